@@ -14,6 +14,13 @@ are resident in HBM before timing starts.
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N>1 through
 torch.distributed.run (one rank per GPU, RCCL over xGMI).  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs and no more: inputs, warmup, the K timed steps, the
+line.  --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+--full adds everything else the line can carry, each measured after the timed region: the
+oracle-digest check of the merged grid, the isolated clear / finalize and serial-call
+re-timings, the secondary marches with their digests, the CPU baselines and the rocprofv3
+PMC / kernel-trace child runs (the options that size them apply under --full only).
 """
 from __future__ import annotations
 
@@ -173,7 +180,7 @@ def pmc_measure(args, log_dir=None):
     if prof is None or under_profiler():
         return None
     tmp = tempfile.mkdtemp(prefix="dmf_pmc_", dir=os.environ.get("TMPDIR", "/tmp"))
-    child = [sys.executable, os.path.abspath(__file__), "--pmc", "off", "--steps", "1", "--warmup", "0",
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--pmc", "off", "--steps", "1", "--warmup", "0",
              "--cpu-frames", "0", "--grid", str(args.grid), "--poses-per-gpu", str(args.poses_per_gpu),
              "--image", args.image, "--serial-ref", "off", "--cpu-reverse-poses", "0"] + (
                  ["--no-secondary"] if args.no_secondary else [])
@@ -288,6 +295,42 @@ def expected_digest(grid, P_total):
         if (e["grid"], e["image"], e["global_poses"], e["seed"]) == (grid, f"{WIDTH}x{HEIGHT}", P_total, 1234):
             return dict(e, key=key)
     return None
+
+
+DUMP_SAMPLE_CELLS = 4 << 20
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, logodds, grid, st, steps):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as
+    out_dir/<name>.npy (float32 / float64, about 50 MB at 512^3), for output-by-output
+    comparison of two builds (the inputs are the same from run to run):
+      logodds_block_sums     float64 (g, g, g): the merged int16 log-odds grid (x-major) summed
+                             over cubic blocks of max(8, grid / 64) cells, so every cell counts
+                             (omitted when the grid is no multiple of the block);
+      logodds_sample         float32: the grid's cells at logodds_sample_cells;
+      logodds_sample_cells   float64: their x-major cell indices, a fixed seeded sample
+                             (DUMP_SEED; with replacement, sorted) of DUMP_SAMPLE_CELLS cells,
+                             or every cell of a grid no larger than that;
+      fuse_counts            float64 [ray-voxel updates, rays, rays with a hit] of one step
+                             (the device's totals over the timed steps / steps: every step
+                             fuses the same frames)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ncell = grid ** 3
+    lo = logodds[:ncell]
+    blk = max(8, grid // 64)
+    if grid % blk == 0:
+        g = grid // blk
+        sums = lo.view(g, blk, g, blk, g, blk).sum(dim=(1, 3, 5), dtype=torch.float64)
+        np.save(os.path.join(out_dir, "logodds_block_sums.npy"), sums.cpu().numpy())
+    if ncell <= DUMP_SAMPLE_CELLS:
+        cells = np.arange(ncell, dtype=np.int64)
+    else:
+        cells = np.sort(np.random.default_rng(DUMP_SEED).integers(0, ncell, size=DUMP_SAMPLE_CELLS, dtype=np.int64))
+    sample = lo[torch.from_numpy(cells).to(lo.device)].to(torch.float32).cpu().numpy()
+    np.save(os.path.join(out_dir, "logodds_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "logodds_sample_cells.npy"), cells.astype(np.float64))
+    np.save(os.path.join(out_dir, "fuse_counts.npy"), np.asarray(st[:3], np.float64) / steps)
 
 
 def host_cores():
@@ -432,7 +475,16 @@ def main():
     ap.add_argument("--print-launch", action="store_true",
                     help="--gpus N > 1 without WORLD_SIZE: print the torch.distributed.run command the bench would "
                          "spawn (JSON) and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline after the timed region (digest "
+                         "check, isolated re-timings, secondary marches, CPU baselines, PMC child runs); without "
+                         "it --pmc, --serial-ref, --cpu-frames, --cpu-reverse-poses and the secondary are off")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if not args.full:
+        args.pmc, args.serial_ref, args.no_secondary = "off", "off", True
+        args.cpu_frames = args.cpu_reverse_poses = 0
     global WIDTH, HEIGHT
     WIDTH, HEIGHT = (int(v) for v in args.image.split("x"))
 
@@ -652,8 +704,12 @@ def main():
                              + ("; they wait for step i+1's phase F to begin (dmf_fuse_set_phase_event)" if phase else "")
                              + ("; pass A of fuse i+1 on libdmf's staging stream beside phase F of fuse i (the 'fuse' span is the "
                                 "compute stream's: batch cut, B and F after waiting for that pass A)" if pipe else "")}
+    elapsed = D.max_over_ranks(elapsed, device=dev)
+    updates, rays, hits = D.sum_over_ranks(st[:3], device=dev)
     # the merged grid of the timed steps (before the isolated re-timings below overwrite it)
-    digest = hashlib.sha256(logodds[:ncell].cpu().numpy().tobytes()).hexdigest()[:16]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, logodds, grid, (updates, rays, hits), args.steps)
+    digest = hashlib.sha256(logodds[:ncell].cpu().numpy().tobytes()).hexdigest()[:16] if args.full else None
     # grid-wide streaming passes, priced separately: clear writes the
     # 2 tiled int32 counter arrays; finalize reads them and writes int16 log-odds.  In the timed
     # steps they run on the comm stream BESIDE the next call's phase F (by design), so their
@@ -670,41 +726,40 @@ def main():
     if world == 1:
         streaming["finalize_span_overlapped"] = rate(merge_ms, fin_bytes, note="event span on the comm stream "
                                                                              "beside the next call's phase F")
-    # isolated re-timing: each pass alone on the compute stream, GPU idle
-    torch.cuda.synchronize(dev)
-    niso = 20
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(3):
-        bufs[0].zero_()
-    e0.record(stream)
-    for _ in range(niso):
-        bufs[0].zero_()
-    e1.record(stream)
-    torch.cuda.synchronize(dev)
-    streaming["clear_isolated"] = rate(e0.elapsed_time(e1) / niso, clear_bytes,
-                                       kernel="torch zero_ of the [hits | misses] int32 counters, alone")
+    if args.full:
+        # isolated re-timing: each pass alone on the compute stream, GPU idle
+        torch.cuda.synchronize(dev)
+        niso = 20
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(3):
+            bufs[0].zero_()
+        e0.record(stream)
+        for _ in range(niso):
+            bufs[0].zero_()
+        e1.record(stream)
+        torch.cuda.synchronize(dev)
+        streaming["clear_isolated"] = rate(e0.elapsed_time(e1) / niso, clear_bytes,
+                                           kernel="torch zero_ of the [hits | misses] int32 counters, alone")
 
-    def fin_whole():
-        _lib.check(L.dmf_fuse_finalize_slab_device(vol._h, bufs[1].data_ptr(), pprm, logodds.data_ptr(), world, -1,
-                                                   stream.cuda_stream))
-    for _ in range(3):
-        fin_whole()
-    e0.record(stream)
-    for _ in range(niso):
-        fin_whole()
-    e1.record(stream)
-    torch.cuda.synchronize(dev)
-    streaming["finalize_isolated"] = rate(e0.elapsed_time(e1) / niso, fin_bytes,
-                                          kernel="dmf::k_finalize over the whole grid (2 x int32 read + int16 "
-                                                 "write per cell), alone")
+        def fin_whole():
+            _lib.check(L.dmf_fuse_finalize_slab_device(vol._h, bufs[1].data_ptr(), pprm, logodds.data_ptr(), world, -1,
+                                                       stream.cuda_stream))
+        for _ in range(3):
+            fin_whole()
+        e0.record(stream)
+        for _ in range(niso):
+            fin_whole()
+        e1.record(stream)
+        torch.cuda.synchronize(dev)
+        streaming["finalize_isolated"] = rate(e0.elapsed_time(e1) / niso, fin_bytes,
+                                              kernel="dmf::k_finalize over the whole grid (2 x int32 read + int16 "
+                                                     "write per cell), alone")
     if st[3] != 0:  # pass B's device-side layout check (dmf_fuse_status): the counters are invalid
         raise RuntimeError(f"fusion layout check failed {st[3]} times")
     _lib.fuse_status(vol)  # raises DmfError(DMF_ERR_DEVICE_CHECK) if any call disagreed
     # how the device cut the calls (the per-volume budget may split a call)
     plan = _lib.fuse_plan(vol, cam, P)
     plan["batches_used_last_call"] = _lib.fuse_batches_used(vol) if plan.get("brick") else 1
-    elapsed = D.max_over_ranks(elapsed, device=dev)
-    updates, rays, hits = D.sum_over_ranks(st[:3], device=dev)
 
     # per-launch algorithmic bytes of the fusion launch (all its kernels), this rank
     upd_launch = float(st[0]) / args.steps
@@ -789,6 +844,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms,
             "higher_is_better": True,
             "scaling": "weak",
@@ -831,17 +887,19 @@ def main():
             "cpu_baseline_multicore": cpu_mt,
             # the reference's own fusion (integratePointCloud, one voxel per point) on the same frames
             "cpu_baseline_reference": cpu_ref,
-            "host_cores": host_cores(),
+            "host_cores": host_cores() if args.full else None,  # the CPU baselines' host
             "step_breakdown_ms": breakdown,
             "streaming": streaming,
             "secondary": secondary,
             # the merged grid after the last step (the same poses every step) against the oracle's
             # digest of the same global poses (tests/golden/gen_fusion_digests.py): the line checks
             # its own exactness at N = 1 and, over the merge, at N > 1
+            # (--full; a plain run leaves the grid on the device)
             "logodds_digest": digest,
             "digest_expected": golden["logodds_digest"] if golden else None,
-            "digest_match": (digest == golden["logodds_digest"]) if golden else None,
-            "digest_source": (f"oracle (CPU restatement) fusion of the {P * world} global poses, "
+            "digest_match": (digest == golden["logodds_digest"]) if golden and digest else None,
+            "digest_source": "not checked (--full checks it)" if digest is None else
+                             (f"oracle (CPU restatement) fusion of the {P * world} global poses, "
                               f"tests/golden/fusion_digests.json[{golden['key']}]") if golden else
                              "no committed oracle digest for this workload",
             "rccl": rccl,

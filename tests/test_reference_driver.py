@@ -1,18 +1,20 @@
-"""The reference's own drivers tests/Raytracing.cpp (:55-105) and tests/SetCover.cpp
-(:218-330), compiled UNCHANGED from /root/reference against the drop-in headers (depth-map-fusion-utils_amd/
-compat first on the include path; headless PCL/Eigen/Boost stand-ins for the I/O,
-downsampling and viewer calls it makes around the hot path) and linked to libdmf.so.
+"""The pipelines of the reference's drivers tests/Raytracing.cpp (:55-105) and tests/SetCover.cpp
+(:218-330) over the drop-in headers (depth-map-fusion-utils_amd/compat first on the include
+path; headless PCL/Eigen/Boost stand-ins for the I/O, downsampling and viewer calls they make
+around the hot path), linked to libdmf.so.
 
-* CPU: the file compiles and links as is (where the reference checkout exists; the
-  binary built by __graft_entry__.build() travels with the tree to the GPU box).
-* GPU: the binary runs headless on a synthetic PCD (ASCII and binary): readPointCloud ->
-  getMinMax3D -> VoxelVolume setup + integratePointCloud -> downsample + positionCameras
-  -> reverseRayTraceFast(camera 0, viz) -> addVolumeWithVoxelsClassified, whose dump is
+* CPU: the reference's own files compile and link UNCHANGED against those headers (where a
+  reference checkout lies beside the repository; they are never copied into it).
+* GPU: compat/examples/pcd_pipeline_headless.cpp, the project's own program making the same
+  calls in the same order (built by __graft_entry__.build() from committed sources alone), runs
+  `visibility` on a synthetic PCD (ASCII and binary): readPointCloud -> getMinMax3D ->
+  VoxelVolume setup + integratePointCloud -> downsample + positionCameras ->
+  reverseRayTraceFast(camera 0, viz) -> addVolumeWithVoxelsClassified, whose dump is
   checked against the oracle running the same sequence: volume geometry, occupied_cells_
   order, the camera pose (against a numpy restatement of VoxelGrid + positionCameras) and
   every voxel's view / good flag;
-* GPU: SetCover.cpp runs headless (its viewer thread ends at once, its input thread runs the
-  pipeline): positionCameras(downsample(cloud, 0.1), 500) filtered to z >= 0, the
+* GPU: its `setcover` mode (a VizThread whose viewer thread ends at once and whose input thread
+  runs the pipeline): positionCameras(downsample(cloud, 0.1), 500) filtered to z >= 0, the
   reverseRayTraceFast good set of every camera, greedySetCover, and writeCameraLocations
   of the selected cameras, which must equal the oracle's selection of the same cameras.
 """
@@ -29,8 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "depth-map-fusion-utils_amd")
 REF_SRC = "/root/reference/tests/Raytracing.cpp"
 REF_SC = "/root/reference/tests/SetCover.cpp"
-BINARY = os.path.join(PKG, "build", "raytracing_ref")
-BINARY_SC = os.path.join(PKG, "build", "setcover_ref")
+BINARY = os.path.join(PKG, "build", "pcd_pipeline_headless")
 K_REF = np.array([602.39306640625, 0.0, 314.6370849609375, 0.0, 602.39306640625, 245.04962158203125, 0.0, 0.0, 1.0],
                  np.float32).reshape(3, 3)  # Raytracing.cpp:61
 
@@ -136,10 +137,10 @@ def test_reference_raytracing_cpp_runs_headless(tmp_path, oracle, binary):
     pcd = tmp_path / "cloud.pcd"
     _write_pcd(pcd, pts, nrm, binary)
     dump = tmp_path / "viz.txt"
-    r = subprocess.run([BINARY, str(pcd)], capture_output=True, text=True, timeout=300,
+    r = subprocess.run([BINARY, "visibility", str(pcd)], capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, DMF_COMPAT_VIZ_DUMP=str(dump)))
     assert r.returncode == 0, r.stdout + r.stderr
-    assert "Volume Integrated" in r.stdout and "Pointcloud Parsed" in r.stdout
+    assert "integrated " in r.stdout and "Pointcloud Parsed" in r.stdout
     d = _parse_dump(dump)
     # Raytracing.cpp:62-75 on the oracle
     lo, hi = pts.min(0), pts.max(0)
@@ -175,13 +176,13 @@ def _read_pose_file(path):
 
 @pytest.mark.gpu
 def test_reference_setcover_cpp_runs_headless(tmp_path, oracle):
-    assert os.path.exists(BINARY_SC), "build it: python -c 'import __graft_entry__ as g; g.build()'"
+    assert os.path.exists(BINARY), "build it: python -c 'import __graft_entry__ as g; g.build()'"
     pts, nrm = Hh.cloud()
     pts, nrm = pts[::2].copy(), nrm[::2].copy()
     pcd = tmp_path / "cloud.pcd"
     _write_pcd(pcd, pts, nrm, True)
     out = tmp_path / "selected.txt"
-    r = subprocess.run([BINARY_SC, str(pcd), str(out)], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([BINARY, "setcover", str(pcd), str(out)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     got = _read_pose_file(out)
     # SetCover.cpp:256-312 on the oracle

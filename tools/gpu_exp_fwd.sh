@@ -9,7 +9,7 @@ tail -2 $O/tests.txt
 for name in rows product rows product; do
   i=$((i+1))
   if [ "$name" = product ]; then lib=depth-map-fusion-utils_amd/build/libdmf.so; else lib=depth-map-fusion-utils_amd/build_exp/$name/libdmf.so; fi
-  DMF_LIB=$lib timeout -k 10 300 python3 bench.py --steps 20 --warmup 2 --pmc off --cpu-frames 0 --cpu-reverse-poses 0 --serial-ref off > $O/${name}_$i.json 2> $O/${name}_$i.err || { echo "FAIL $name"; tail -5 $O/${name}_$i.err; exit 2; }
+  DMF_LIB=$lib timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 2 --pmc off --cpu-frames 0 --cpu-reverse-poses 0 --serial-ref off > $O/${name}_$i.json 2> $O/${name}_$i.err || { echo "FAIL $name"; tail -5 $O/${name}_$i.err; exit 2; }
   python3 -c "import json; b=json.load(open('$O/${name}_$i.json')); s=b['secondary']; f=s['forward_first_hits']; print('$name', {k: f[k] for k in f if 'ms' in k}, s['reverse_ray_trace_fast']['ms_per_batch'])"
 done
 echo FWDOK

@@ -34,7 +34,7 @@ with open(os.path.join(dst, "pmc_per_kernel.csv"), "w", newline="") as f:
         n = len(ndisp[(k, c)])
         w.writerow([k, c, f"{v:.0f}", n, f"{v / n:.1f}"])
 if not os.path.exists(os.path.join(src, "bench_kt.json")):
-    # a bench.py --pmc-dir directory (the bench line carries its own summary): counters and
+    # a bench.py --full --pmc-dir directory (the bench line carries its own summary): counters and
     # kernel statistics only
     sys.exit(0)
 bench = json.load(open(os.path.join(src, "bench_kt.json")))
