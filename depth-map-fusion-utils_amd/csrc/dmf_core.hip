@@ -686,6 +686,8 @@ static void free_state(dmf_volume* v) {
   v->sorder_valid = false;
   for (auto& s : v->scratch) f(s.first);
   v->scratch.clear();
+  v->bk_last_bt = nullptr;  // pointed into the scratch just freed (dmf_fuse_batches_used reads it)
+  v->last_kernel = nullptr;  // no fusion call yet on the new volume
   v->d_occ = nullptr; v->d_brick = nullptr; v->d_bdist = nullptr; v->bdist_valid = false; v->d_slot_of = nullptr; v->d_hash = nullptr; v->d_view = nullptr; v->d_good = nullptr;
   v->d_pts = nullptr; v->d_pnrm = nullptr; v->d_pslot = nullptr; v->d_off = nullptr; v->d_csr_nrm = nullptr;
   v->d_csr_pts = nullptr; v->d_axes = nullptr; v->d_enum = nullptr;

@@ -254,6 +254,19 @@ class VoxelVolume:
         check(self._L.dmf_volume_voxel_points(self._h, int(hash_), ptr(p), ptr(q), n.value, C.addressof(n)))
         return p[:n.value], q[:n.value]
 
+    def export(self):
+        """dmf_volume_export: every voxel's points in one call -> (offsets int32 (V + 1,), pts
+        float32 (n, 3), normals4 float32 (n, 4)); the points of slot s (occupied_cells_ order) are
+        rows offsets[s]:offsets[s + 1] in insertion order, normals4[:, 3] = 1 where the point
+        carried a normal."""
+        i = self.info()
+        V, n = int(i["num_occupied"]), int(i["num_points"])
+        off = np.zeros(V + 1, np.int32)
+        pts = np.zeros((max(n, 1), 3), np.float32)
+        nrm = np.zeros((max(n, 1), 4), np.float32)
+        check(self._L.dmf_volume_export(self._h, ptr(off), ptr(pts), ptr(nrm), n))
+        return off, pts[:n], nrm[:n]
+
     def occupancy_dense(self):
         nx, ny, nz = self.dims
         out = np.zeros(nx * ny * nz, np.uint8)

@@ -52,6 +52,19 @@ struct Aff { float m[3][4]; };
 // product), dot(), squaredNorm() and the 3x3 cofactor determinant.
 static inline float sum3(float a0, float a1, float a2) { return a0 + (a1 + a2); }
 
+// A double stored into a float variable, as `float x = <double expression>` does in the
+// reference.  The store goes through a volatile so that it is really made: g++ 11.4 -O3 pairs
+// the x and y lanes of reverseRayTraceFast's voxel corner in its SLP vectoriser and then drops
+// their narrowing, which leaves the centroid (float)(id * delta + min + delta / 2) instead of
+// (float)((float)(id * delta + min) + delta / 2).  The two differ by one float ulp for about one
+// voxel in 10^4 when delta is no power of two and the grid lies far from the origin (64-bit
+// intermediate, 24-bit result: a double rounding), and such a centroid sends the 1 mm march
+// through other cells.
+static inline float narrow(double v) {
+  volatile float f = (float)v;
+  return f;
+}
+
 static inline Aff load_aff(const float* T) {
   Aff a;
   for (int i = 0; i < 3; ++i)
@@ -409,9 +422,9 @@ int64_t orc_reverse_ray_trace_fast(orc_volume* vol, const float* K, int H, int W
   for (uint64_t hashes : vol->occupied_cells_) {
     int xid, yid, zid;
     orc_volume::voxel_coords(hashes, xid, yid, zid);
-    const float x = (float)(xid * vol->xdelta_ + vol->xmin_);
-    const float y = (float)(yid * vol->ydelta_ + vol->ymin_);
-    const float z = (float)(zid * vol->zdelta_ + vol->zmin_);
+    const float x = narrow(xid * vol->xdelta_ + vol->xmin_);
+    const float y = narrow(yid * vol->ydelta_ + vol->ymin_);
+    const float z = narrow(zid * vol->zdelta_ + vol->zmin_);
     Voxel* voxel = vol->voxels_[xid][yid][zid];
     float centroid[3] = {(float)(x + vol->xdelta_ / 2.0), (float)(y + vol->ydelta_ / 2.0),
                          (float)(z + vol->zdelta_ / 2.0)};

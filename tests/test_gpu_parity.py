@@ -599,7 +599,8 @@ def test_golden_config1_gpu(dmf):
 def test_forward_first_hits_batched_device(oracle, engine, oeng, dmf, fwd_kernel):
     """dmf_forward_first_hits_device over P poses in one launch == the oracle per pose (every
     batched kernel, DMF_KNOB_FWD_KERNEL: 0 = the (tile block, pose) grid, 1 = per-XCD unit
-    queues, 2 = per-wave lane refill k_forward_q; odd strides give partial 8x8 tiles)."""
+    queues, 2 = per-wave lane refill k_forward_q).  The (3, 2) lattice is 160 x 320: whole 8x8
+    tiles only; lattices that end in partial tiles are in test_gpu_shapes.py."""
     import ctypes as C
     from dmf_amd import _lib
     ov = Hh.oracle_volume(oracle, n=100)

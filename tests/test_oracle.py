@@ -328,3 +328,43 @@ def test_fusion_digest_fixture_reproduces():
         assert k in table and len(table[k]["logodds_digest"]) == 16
     got = G.oracle_digest(*G.WORKLOADS["config2_N1"], threads=os.cpu_count() or 1)
     assert got == table["config2_N1"]
+
+
+def test_reverse_fast_centroid_is_narrowed_twice(oracle):
+    """reverseRayTraceFast stores the voxel corner in float variables before it adds delta / 2
+    (RayTracingEngine.hpp:148-157): the centroid is (float)((float)(id * delta + min) + delta / 2),
+    not (float)(id * delta + min + delta / 2).  In the grid [-2001, -2000] on y with 100 cells the
+    two differ by one float ulp for voxel (51, 31, 66); with the first the march's first sample
+    (50 mm) toward the camera below lies in cell (55, 33, 68), with the second in (55, 32, 68).
+    An optimised build of the oracle once dropped the first narrowing: each of the two cells is
+    tried as the only occluder."""
+    f32, f64 = np.float32, np.float64
+    bounds = (999.5, 1000.5, -2001.0, -2000.0, 332.8, 333.8)
+    mn, dl, vox = bounds[0::2], 0.01, (51, 31, 66)
+    T = np.array([1.1235414e-03, 6.7889744e-01, -7.3423225e-01, 1000.5180053710938,
+                  9.9981278e-01, -1.4945699e-02, -1.2289389e-02, -2000.5,
+                  -1.9316848e-02, -7.3408097e-01, -6.7878711e-01, 333.7676696777344], np.float32)
+    # the reference's arithmetic restated in numpy scalars
+    cen = [f32(f64(f32(f64(vox[a]) * dl + mn[a])) + dl / 2.0) for a in range(3)]
+    once = [f32(f64(vox[a]) * dl + mn[a] + dl / 2.0) for a in range(3)]
+    assert cen[1] != once[1] and cen[0] == once[0] and cen[2] == once[2]
+    d = [T[3 + 4 * a] - cen[a] for a in range(3)]
+    q = np.sqrt(f32(d[0] * d[0]) + (f32(d[1] * d[1]) + f32(d[2] * d[2])))
+    p = [cen[a] + f32(f32(d[a] / q) * f32(50)) / f32(1000.0) for a in range(3)]
+    assert all(type(x) is np.float32 for x in p)
+    assert [int(np.floor((f64(p[a]) - mn[a]) / dl)) for a in range(3)] == [55, 33, 68]
+    lo = np.array(mn)
+    eng = oracle.Engine(np.array([602.39306640625, 0, 314.6370849609375, 0, 602.39306640625, 245.04962158203125,
+                                  0, 0, 1], np.float32))
+    seen = {}
+    for occluder in ((55, 33, 68), (55, 32, 68)):
+        v = oracle.Volume()
+        v.setDimensions(*bounds)
+        v.setVolumeSize(100, 100, 100)
+        v.constructVolume()
+        pts = np.stack([(lo + (np.array(c) + 0.5) * dl).astype(np.float32) for c in (vox, occluder)])
+        v.integratePointCloud(pts, np.tile(np.array([[0, 0, 1]], np.float32), (2, 1)))
+        assert [int(h) >> 40 for h in v.occupied_cells_] == [vox[0], occluder[0]]
+        eng.reverseRayTraceFast(v, T, True)
+        seen[occluder] = int(v.voxel_table()[0][0])
+    assert seen == {(55, 33, 68): 0, (55, 32, 68): 1}
