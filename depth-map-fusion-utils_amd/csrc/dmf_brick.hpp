@@ -353,6 +353,85 @@ __host__ __device__ inline int coarse_next(Coarse& w) {
   return s2 ? 2 : (s1 ? 1 : 0);
 }
 
+// ---- The coarse walk on scaled 32-bit state (pass A) ----
+//
+// Every coarse K is kB * 2Q|dq| = 2^14 |dq| (kB = 32), and every update of E01 / E02 / E12 adds
+// or subtracts one K, so E mod 2^14 never changes along a coarse walk, and every test of
+// coarse_next is E > 0 <=> E - 1 >= 0 <=> floor((E - 1) / 2^14) >= 0.  Hence the walk runs
+// EXACTLY on gamma = (E - 1) >> 14 (arithmetic shift = floor division) with increments |dq|
+// instead of K: the low 14 bits of E - 1 never influence a decision (the beta trick of the
+// 20-byte pair record below).  Range: E_ab = |dq_a||dq_b| (tau_a - tau_b) with
+// tau_a = H_a / |dq_a| the time of axis a's next boundary crossing.  After the event at time
+// t, the axis that stepped has tau = t + 2^14 / |dq|, every other moving axis t <= tau <= (the
+// time of its own last step, or 0) + 2^14 / |dq| (the first boundary: H <= 2Q (k0 + 1) <= 2^14,
+// h0 <= 2Q, k0 <= kB - 1), so |tau_a - tau_b| <= 2^14 / min(|dq_a|, |dq_b|) and
+//   |E_ab| <= 2^14 max(|dq_a|, |dq_b|),   |gamma_ab| <= max(|dq_a|, |dq_b|) + 1 < 2^19 + 1
+// for 19-bit ray records (2^18 + 1 on the brick path's grids of <= 1024 cells per axis); the
+// self-test asserts it (coarse_gamma_ok).  A pair with a non-moving axis holds +-kNever32
+// (only its sign is ever used; both non-moving: -1, as E = 0).  Such an axis never steps, but
+// its |dq| (< 2Q: the ray stays in one cell along it) is still added when the pair's other
+// axis steps: at most 2Q * total < 2^15 over a walk, far from a sign change of +-2^30.
+// gamma(0) comes from coarse_init's own products H_a |dq_b| - H_b |dq_a| in 64 bits, once per
+// ray.  Checked step by step against coarse_next by tools/coarse32_selftest.cpp.
+static_assert(kB * 2 * kQ == (1 << (kLog + 9)), "coarse K = 2^(kLog + 9) |dq|");
+constexpr int kCoarseShift = kLog + 9;
+constexpr int32_t kNever32 = 1 << 30;
+struct Coarse32 {
+  int32_t g01, g02, g12;  // gamma of E01, E02, E12 at the next boundary crossings
+  int32_t d0, d1, d2;     // |dq| per axis (the gamma walk's K)
+  int32_t total;          // boundary crossings of the whole ray
+};
+
+__host__ __device__ inline void coarse_init32(const QRay& r, Coarse32& w) {
+  int32_t H[3];  // <= 2Q kB = 2^14: 32x32-bit products below
+  w.total = coarse_total(r);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int32_t off = r.cs[a] & (kB - 1);
+    const int32_t k0 = r.st[a] > 0 ? kB - 1 - off : off;  // first boundary crossing
+    H[a] = r.h0[a] + (int32_t)(2 * kQ) * k0;
+  }
+  auto pr = [&](int a, int b) -> int32_t {
+    if (r.st[a] && r.st[b]) {
+      // (0 <= H <= 2^14, 0 <= |dq| < 2^19: products of unsigned 24-bit values, for which the
+      // device has full-rate multiplies; the signed 64-bit product took two 64-bit mads each)
+      auto mul = [](int32_t x, int32_t y) {
+        return (int64_t)((uint64_t)((uint32_t)x & 0xffffffu) * ((uint32_t)y & 0xffffffu));
+      };
+      const int64_t E = mul(H[a], r.adq[b]) - mul(H[b], r.adq[a]);
+      return (int32_t)((E - 1) >> kCoarseShift);
+    }
+    return r.st[a] ? -kNever32 : (r.st[b] ? kNever32 : -1);
+  };
+  w.g01 = pr(0, 1);
+  w.g02 = pr(0, 2);
+  w.g12 = pr(1, 2);
+  w.d0 = r.adq[0];
+  w.d1 = r.adq[1];
+  w.d2 = r.adq[2];
+}
+
+// coarse_next on the scaled state: the same tests, selections and x < y < z tie order.
+__host__ __device__ inline int coarse_next32(Coarse32& w) {
+  const bool b10 = w.g01 >= 0;
+  const bool s2 = (b10 ? w.g12 : w.g02) >= 0;
+  const bool s1 = !s2 && b10, s0 = !s2 && !b10;
+  w.g01 += s0 ? w.d1 : (s1 ? -w.d0 : 0);
+  w.g02 += s0 ? w.d2 : (s2 ? -w.d0 : 0);
+  w.g12 += s1 ? w.d2 : (s2 ? -w.d1 : 0);
+  return s2 ? 2 : (s1 ? 1 : 0);
+}
+
+// The self-test's range check of a walk state: every pair of two moving axes within the bound.
+__host__ __device__ inline bool coarse_gamma_ok(const QRay& r, const Coarse32& w) {
+  auto ok = [&](int a, int b, int32_t g) {
+    if (!r.st[a] || !r.st[b]) return true;
+    const int32_t m = (r.adq[a] > r.adq[b] ? r.adq[a] : r.adq[b]) + 1;
+    return g <= m && g >= -m;
+  };
+  return ok(0, 1, w.g01) && ok(0, 2, w.g02) && ok(1, 2, w.g12);
+}
+
 // coarse_next without its state: the axis of the next brick-boundary crossing of a ray now in
 // brick coordinates (b0, b1, b2).  On each moving axis the next boundary is fine crossing
 // k_a (into brick b_a + st_a); the earliest of those events in (T, axis) order (ev_before:
@@ -409,6 +488,48 @@ __host__ __device__ inline uint64_t path_put(uint64_t path, int t, int a) {
   return t < kPathSteps ? path | (uint64_t)a << (2 * t) : path;
 }
 __host__ __device__ inline int path_axis(uint64_t path, int t) { return (int)(path >> (2 * t)) & 3; }
+// The same path as two 32-bit words (lo: steps 0-15, hi: steps 16-31; path = lo | hi << 32).
+// The step number t of the coarse walk is the same in every active lane of a wave (the loop
+// counter), so on the device the word is chosen by a scalar branch and the shift amount is a
+// scalar: one 32-bit shift-or (pass A) / one bit-field extract (pass B) per step instead of a
+// 64-bit shift by a per-lane amount.  (By value, on plain locals of the caller: a word chosen
+// through a reference became a select of addresses and both words went to scratch memory.)
+__host__ __device__ inline uint32_t path_word_put(uint32_t word, int t, int a) {
+  return word | (uint32_t)a << ((2 * t) & 31);
+}
+// a value that is the same in every active lane of the wave, as a scalar
+__host__ __device__ inline int wave_uniform(int x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_readfirstlane(x);
+#else
+  return x;
+#endif
+}
+
+// Pass A's coarse walk of one ray: calls f(brick index) for every brick the ray passes, in
+// order, and returns the recorded path (= path_put of every boundary's axis).  b = the index of
+// the ray's first brick, D0 / D1 / D2 = the index step of a boundary crossing along x / y / z
+// (st * nb1 * nb2, st * nb2, st): no brick coordinates are kept.  The walk runs on the scaled
+// 32-bit state above.  (Selects, not axis-indexed arrays: those become scratch memory.)
+template <class F>
+__host__ __device__ inline uint64_t coarse_walk32(const QRay& r, int32_t b, int32_t D0, int32_t D1, int32_t D2,
+                                                  F&& f) {
+  uint32_t lo = 0, hi = 0;
+  f(b);
+  Coarse32 cw;
+  coarse_init32(r, cw);
+  for (int t = 0; t < cw.total; ++t) {
+    const int a = coarse_next32(cw);
+    b += a == 2 ? D2 : (a == 1 ? D1 : D0);  // (the tests coarse_next32 made: no compare of a)
+    f(b);
+    const int ts = wave_uniform(t);  // the loop counter
+    if (ts < kPathSteps / 2) lo = path_word_put(lo, ts, a);
+    else if (ts < kPathSteps) hi = path_word_put(hi, ts, a);
+  }
+  return (uint64_t)lo | (uint64_t)hi << 32;
+}
+// the axis of step t < kPathSteps from its word (lo for t < 16, hi for 16 <= t < 32)
+__host__ __device__ inline int path_axis2(uint32_t word, int t) { return (int)(word >> ((2 * t) & 31)) & 3; }
 
 // ---- Major-axis ("slab") form of the fine walk (phase F) ----
 //

@@ -531,21 +531,15 @@ __device__ inline int bk_index(const BkGeom& bg, int x, int y, int z) {
   return bk::mul24(bk::mul24(x, bg.nb[1]) + y, bg.nb[2]) + z;  // (24-bit multiplies, dmf_brick.hpp mul24)
 }
 
-// Coarse walk of one ray: calls f(brick index, axis of the boundary crossed to enter it
-// (-1 for the first brick), brick coordinates) for every brick it passes, in order.
+// Coarse walk of one ray (pass A): calls f(brick index) for every brick it passes, in order,
+// and returns the crossing axes of its first kPathSteps boundaries (pass B replays them).
+// dmf_brick.hpp coarse_walk32: the scaled 32-bit walk, the brick index moved by a per-axis
+// step as in pass B's replay, no brick coordinates.
 template <class F>
-__device__ inline void bk_coarse(const BkGeom& bg, const bk::QRay& R, F&& f) {
-  int b0 = R.cs[0] >> bk::kLog, b1 = R.cs[1] >> bk::kLog, b2 = R.cs[2] >> bk::kLog;
-  f(bk_index(bg, b0, b1, b2), -1, b0, b1, b2);
-  bk::Coarse cw;
-  bk::coarse_init(R, cw);
-  for (int t = 0; t < cw.total; ++t) {
-    const int a = bk::coarse_next(cw);
-    b0 += a == 0 ? R.st[0] : 0;
-    b1 += a == 1 ? R.st[1] : 0;
-    b2 += a == 2 ? R.st[2] : 0;
-    f(bk_index(bg, b0, b1, b2), a, b0, b1, b2);
-  }
+__device__ inline uint64_t bk_coarse(const BkGeom& bg, const bk::QRay& R, F&& f) {
+  const int b = bk_index(bg, R.cs[0] >> bk::kLog, R.cs[1] >> bk::kLog, R.cs[2] >> bk::kLog);
+  const int32_t D0 = bk::mul24(R.st[0], bg.nb[1] * bg.nb[2]), D1 = bk::mul24(R.st[1], bg.nb[2]), D2 = R.st[2];
+  return bk::coarse_walk32(R, b, D0, D1, D2, f);
 }
 
 // Wave-aggregated LDS histogram add: the lanes of a packet walk near-parallel rays and
@@ -721,8 +715,7 @@ __device__ inline void bk_rays_wg(const BkRaysArgs& A_, unsigned wg, uint32_t* h
       bk::qray_from(qs32, qe32, inside, R);  // = decode_ray(A, B), without the round trip
       upd += (unsigned long long)(R.nsteps + 1);
       nhit += inside ? 1 : 0;
-      int t = 0;
-      bk_coarse(bg, R, [&](int b, int a, int, int, int) {
+      path = bk_coarse(bg, R, [&](int b) {
 #if defined(DMF_EXP_A_AGG_LOOP)  // experiment builds: the loop over every distinct brick
         if constexpr (HASH) hash_add_agg(hist, hmask, hshift, b, &sh[1]);
         else hist_add_agg<H16>(hist, b);
@@ -731,7 +724,6 @@ __device__ inline void bk_rays_wg(const BkRaysArgs& A_, unsigned wg, uint32_t* h
         if constexpr (HASH) hash_add_first(hist, hmask, hshift, b, &sh[1]);
         else hist_add_first<H16>(hist, b);
 #endif
-        if (a >= 0) path = bk::path_put(path, t++, a);
       });
     }
     nvalid += valid ? 1 : 0;
@@ -1049,7 +1041,15 @@ __global__ __launch_bounds__(1024) void k_bk_scan(int nbricks, const uint32_t* _
 // scan (k_bk_scan) in ONE workgroup: one launch instead of three on the chain between pass A
 // and pass B of a pipelined call (config 2: 512 bricks, 64 poses; the chain's launch gaps
 // and three kernels ~47 us of a 1.7-ms call).
+// (experiment builds DMF_EXP_LAYOUT1_BRICKS = 4096: the headline's 512^3 on this path too; its
+// 16 KB of counts beside the scan body's 12 KB no longer fit next to phase F's box, and one
+// workgroup reads the 2 MB of per-pose counts alone: measured in DESIGN.md §5.4)
+#if defined(DMF_EXP_LAYOUT1_BRICKS)
+constexpr int kBkLayout1Bricks = DMF_EXP_LAYOUT1_BRICKS, kBkLayout1Poses = 256;
+static_assert(kBkLayout1Bricks <= 4096, "bk_scan_body<false> holds <= 4 counts per lane");
+#else
 constexpr int kBkLayout1Bricks = 1024, kBkLayout1Poses = 256;
+#endif
 __global__ __launch_bounds__(1024) void k_bk_layout1(int P, const unsigned long long* __restrict__ pose_pairs,
                                                      unsigned long long cap, int max_poses, uint32_t* __restrict__ bt,
                                                      int nbricks, int j, const uint32_t* __restrict__ pose_cnt,
@@ -1368,6 +1368,7 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
 #endif
     uint32_t slot = DMF_B_SLOT(b);
     extra = 0;
+    uint32_t pword = (uint32_t)path;  // the path word of the current step (steps 0-15: the low one)
     for (int t = 0; t < total; ++t) {
 #if defined(DMF_EXP_STATS)
       {  // diagnostic build: the replay loop's wave iterations and the lanes active in them
@@ -1378,9 +1379,13 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
         }
       }
 #endif
+      // (t is the loop counter, the same in every active lane: the path word is chosen by a
+      // scalar branch and the axis is one bit-field extract at a scalar offset, path_axis2)
       int a;
-      if (t < bk::kPathSteps) a = bk::path_axis(path, t);
-      else a = bk::coarse_next_k(R, P0, P1, P2);  // (branch: skipped by the waves whose lanes all replay)
+      if (t < bk::kPathSteps) {
+        if (t == bk::kPathSteps / 2) pword = (uint32_t)(path >> 32);
+        a = bk::path_axis2(pword, t);
+      } else a = bk::coarse_next_k(R, P0, P1, P2);  // (branch: skipped by the waves whose lanes all replay)
       b += a == 0 ? D0 : (a == 1 ? D1 : D2);
       const int32_t k = a == 0 ? P0 : (a == 1 ? P1 : P2);
       P0 += a == 0 ? bk::kB : 0;
