@@ -21,9 +21,16 @@
 
 namespace dmf_compat {
 
+// DMF_COMPAT_SUM3_LEFT: the other association, (a0 + a1) + a2.  Only the reference pin
+// (oracle/ref_pin) sets it, to show how much of a result rests on the summation order.
+#ifdef DMF_COMPAT_SUM3_LEFT
+inline float sum3(float a0, float a1, float a2) { return (a0 + a1) + a2; }
+#else
 inline float sum3(float a0, float a1, float a2) { return a0 + (a1 + a2); }
+#endif
 
 struct Vector3f {
+  using Scalar = float;
   float v[3] = {0.f, 0.f, 0.f};
   Vector3f() = default;
   explicit Vector3f(int) {}  // Eigen's Vector3f p1(3) idiom
@@ -43,6 +50,10 @@ struct Vector3f {
   // Eigen promotes a double scalar to the float Scalar before the coefficient-wise op
   Vector3f operator*(double s) const { const float f = (float)s; return {v[0] * f, v[1] * f, v[2] * f}; }
   Vector3f operator/(double s) const { const float f = (float)s; return {v[0] / f, v[1] / f, v[2] / f}; }
+  // coefficient-wise, in Eigen's order: a += b is a = a + b, a /= s divides by the float s
+  Vector3f& operator+=(const Vector3f& o) { for (int i = 0; i < 3; ++i) v[i] = v[i] + o.v[i]; return *this; }
+  Vector3f& operator/=(double s) { const float f = (float)s; for (int i = 0; i < 3; ++i) v[i] = v[i] / f; return *this; }
+  friend Vector3f operator*(float s, const Vector3f& a) { return {s * a.v[0], s * a.v[1], s * a.v[2]}; }
   float dot(const Vector3f& o) const { return sum3(v[0] * o.v[0], v[1] * o.v[1], v[2] * o.v[2]); }
   // Eigen cross(): (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0)
   Vector3f cross(const Vector3f& o) const {

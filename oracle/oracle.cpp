@@ -5,12 +5,14 @@
 // links, loads or calls this file.  Only tests/, __graft_entry__.smoke() and
 // bench.py's cpu_baseline leg use it, and only as the checker / CPU baseline.
 //
-// PARITY UNPINNED: the reference (REXJJ/depth-map-fusion-utils) ships no golden
-// vectors, fixtures or assertions for this path, and it cannot be
-// built here (Eigen3/PCL/OpenCV/Boost/octomap/nlopt absent).  This
-// restatement follows the reference source line by line (file:line cited at every
-// function) with the evaluation-order spec of DESIGN.md §3; a second, independent
-// pure-Python restatement (oracle/py_oracle.py) cross-checks it on small cases.
+// PARITY: the reference (REXJJ/depth-map-fusion-utils) ships no golden vectors,
+// fixtures or assertions for this path.  This restatement follows the
+// reference source line by line (file:line cited at every function) with the
+// evaluation-order spec of DESIGN.md §3.  It is pinned to the reference's own headers,
+// compiled unchanged and run on the CPU (oracle/ref_pin/, tests/golden/ref_pin_*.npz,
+// tests/test_reference_pin.py; DESIGN.md §2 says what that pins and what it cannot);
+// a second, independent pure-Python restatement (oracle/py_oracle.py) cross-checks it
+// on small cases, the parts outside the reference's headers included.
 //
 // Data layout is the REFERENCE layout on purpose (vector<vector<vector<Voxel*>>>
 // with per-voxel point/normal vectors, Volume.hpp:29-61) so that timing it is an
@@ -281,6 +283,11 @@ void orc_get_info(const orc_volume* v, double* d, int* dims, uint64_t* hsize) {
 }
 
 int64_t orc_hazards(const orc_volume* v) { return v->hazards; }
+// Volume.hpp:230-233 validPoints and :150-156 getVoxel on their own
+int orc_valid_points(const orc_volume* v, float x, float y, float z) { return v->valid_points(x, y, z) ? 1 : 0; }
+void orc_get_voxel(const orc_volume* v, float x, float y, float z, int* out) {
+  v->get_voxel(x, y, z, out[0], out[1], out[2]);
+}
 
 // Volume.hpp:172-197 (no normals: NO validCoords guard -> hazard) and
 // Volume.hpp:199-228 (with normals: guarded).  Returns the number of points binned.
@@ -357,6 +364,9 @@ void orc_occupancy_dense(const orc_volume* v, uint8_t* out) {
 }
 
 // ---- Camera helpers (Camera.hpp) -----------------------------------------
+static Cam make_cam_hw(int H, int W) {
+  Cam c; std::memset(c.K, 0, sizeof(c.K)); c.height = H; c.width = W; return c;
+}
 void orc_project_point(const float* K, int r, int c, int d, float* out) {
   Cam cam; std::memcpy(cam.K, K, sizeof(cam.K)); cam.project(r, c, d, out);
 }
@@ -371,6 +381,7 @@ void orc_inverse_pose(const float* T, float* out) {
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 4; ++j) out[i * 4 + j] = r.m[i][j];
 }
+int orc_valid_pixel(int H, int W, int r, int c) { return make_cam_hw(H, W).valid_pixel(r, c) ? 1 : 0; }
 int orc_degree(double radian) { return degree_x86(radian); }
 int orc_angle_ok(const float* n, const float* v) { return angle_ok(Nrm{{n[0], n[1], n[2]}}, v) ? 1 : 0; }
 

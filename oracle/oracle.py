@@ -52,6 +52,8 @@ def lib():
         "orc_construct": (C.c_int, [_vp]),
         "orc_get_info": (None, [_vp, _f64p, _i32p, _u64p]),
         "orc_hazards": (C.c_int64, [_vp]),
+        "orc_valid_points": (C.c_int, [_vp, C.c_float, C.c_float, C.c_float]),
+        "orc_get_voxel": (None, [_vp, C.c_float, C.c_float, C.c_float, _i32p]),
         "orc_integrate": (C.c_int64, [_vp, _f32p, _vp, C.c_int64]),
         "orc_num_occupied": (C.c_int64, [_vp]),
         "orc_occupied": (C.c_int64, [_vp, _u64p, C.c_int64]),
@@ -63,6 +65,7 @@ def lib():
         "orc_deproject_point": (None, [_f32p, C.c_double, C.c_double, C.c_double, _i32p]),
         "orc_transform_point": (None, [_f32p, C.c_double, C.c_double, C.c_double, _f32p]),
         "orc_inverse_pose": (None, [_f32p, _f32p]),
+        "orc_valid_pixel": (C.c_int, [C.c_int] * 4),
         "orc_degree": (C.c_int, [C.c_double]),
         "orc_angle_ok": (C.c_int, [_f32p, _f32p]),
         "orc_backproject": (None, [_f32p, C.c_int, C.c_int, _u16p, _f32p, _f32p]),
@@ -129,6 +132,11 @@ def inverse_pose(T):
     out = np.zeros(12, np.float32)
     lib().orc_inverse_pose(_f32(T, 12), out)
     return out
+
+
+def valid_pixel(H, W, r, c):
+    """Camera.hpp:65-68 validPixel."""
+    return bool(lib().orc_valid_pixel(int(H), int(W), int(r), int(c)))
 
 
 def degree(rad):
@@ -199,6 +207,16 @@ class Volume:
 
     def hazards(self):
         return lib().orc_hazards(self._h)
+
+    def validPoints(self, x, y, z):
+        """Volume.hpp:230-233."""
+        return bool(lib().orc_valid_points(self._h, float(x), float(y), float(z)))
+
+    def getVoxel(self, x, y, z):
+        """Volume.hpp:150-156."""
+        out = np.zeros(3, np.int32)
+        lib().orc_get_voxel(self._h, float(x), float(y), float(z), out)
+        return int(out[0]), int(out[1]), int(out[2])
 
     def integratePointCloud(self, xyz, normals=None):
         """Volume.hpp:172-228. Returns number of points binned."""
