@@ -219,6 +219,7 @@ int dmf_fuse_merge_finalize_device(dmf_volume* v, int32_t* d_counters, const dmf
   DMF_TRY(require_constructed(v));
   const hipStream_t st = stream ? (hipStream_t)stream : v->stream;
   if (!d_counters || !prm || !d_logodds) return fail(DMF_ERR_INVALID, "null argument");
+  DMF_TRY(check_finalize_params(prm));  // before the reduce-scatter: the counters stay untouched
   int nr = 1, rk = 0;
   if (comm) DMF_TRY(comm_shape(comm, &nr, &rk));  // NULL: one rank, no collective
   const dmf_merge_plan p = merge_plan(v, nr, rk);

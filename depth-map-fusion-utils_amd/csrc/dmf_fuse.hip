@@ -2515,8 +2515,18 @@ static int fuse_bricks(dmf_volume* v, const CamP& cp, const Geom& g, const uint1
   return DMF_OK;
 }
 
+// The clamp of k_finalize narrows to int16 and takes l_min first: outside these ranges the
+// cast would wrap and the restatements (oracle, dist.finalize_tiles_np) would disagree.
+int check_finalize_params(const dmf_fuse_params* prm) {
+  if (prm->l_min > prm->l_max || prm->l_min < -32768 || prm->l_max > 32767)
+    return fail(DMF_ERR_INVALID, "log-odds clamp [%d, %d] must satisfy -32768 <= l_min <= l_max <= 32767", prm->l_min,
+                prm->l_max);
+  return DMF_OK;
+}
+
 int finalize_tiles(dmf_volume* v, const int32_t* d_hits, const int32_t* d_misses, const dmf_fuse_params* prm,
                    int16_t* d_out, int64_t t0, int64_t t1, hipStream_t stream) {
+  DMF_TRY(check_finalize_params(prm));
   if (t1 <= t0) return DMF_OK;
   const int64_t lanes = (t1 - t0) * 4;  // four lanes per 2x2x4 tile
   hipLaunchKernelGGL(k_finalize, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, v->geom(), d_hits,

@@ -92,7 +92,10 @@ CamP cam_params(const dmf_camera* c);
 
 // Fusion finalize over tiled counters, tiles [t0, t1) (dmf_fuse.hip); the tiled layout's
 // x extent in 2-cell tile rows and tiles per row (a contiguous tile range of whole rows is
-// an x slab of the grid).
+// an x slab of the grid).  finalize_tiles rejects clamp bounds outside int16 or inverted
+// (check_finalize_params: DMF_ERR_INVALID, nothing launched); the merge calls the check
+// itself before its collectives, which change the counters.
+int check_finalize_params(const dmf_fuse_params* prm);
 int finalize_tiles(dmf_volume* v, const int32_t* d_hits, const int32_t* d_misses, const dmf_fuse_params* prm,
                    int16_t* d_out, int64_t t0, int64_t t1, hipStream_t stream);
 int tile_rows(const dmf_volume* v, int64_t* ntx, int64_t* tiles_per_row);

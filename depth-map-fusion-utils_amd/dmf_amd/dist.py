@@ -141,8 +141,11 @@ def to_tiled(lin, dims, n_pad):
 
 
 def finalize_tiles_np(hits_t, miss_t, dims, l_hit, l_miss, l_min, l_max, out, t0, t1):
-    """k_finalize over tiles [t0, t1) in numpy: writes out[x, y, z] (x-major int16)."""
+    """k_finalize over tiles [t0, t1) in numpy: writes out[x, y, z] (x-major int16).  The clamp
+    bounds libdmf rejects (l_min > l_max or outside int16) raise ValueError, out untouched."""
     import numpy as np
+    if l_min > l_max or l_min < -32768 or l_max > 32767:
+        raise ValueError(f"log-odds clamp [{l_min}, {l_max}] must satisfy -32768 <= l_min <= l_max <= 32767")
     nx, ny, nz = dims
     nty, ntz = (ny + 1) // 2, (nz + 3) // 4
     for t in range(t0, t1):

@@ -72,7 +72,16 @@ typedef struct dmf_volume_info {
   int64_t hazards;       /* unguarded out-of-range accesses the reference would make */
 } dmf_volume_info;
 
-/* 3D-DDA log-odds fusion parameters (not in the reference). */
+/* 3D-DDA log-odds fusion parameters (not in the reference).
+ * Depth gate: any int32 pair.  A pixel of depth d (uint16, 0..65535) is traced iff
+ * dmin_mm <= d < dmax_mm, so an empty or inverted gate (dmin_mm >= dmax_mm) traces nothing,
+ * dmin_mm <= 0 admits d = 0 (a ray that ends at the camera centre: one update in the camera's
+ * cell when that lies in the grid) and dmax_mm > 65535 admits d = 65535.
+ * Clamp: -32768 <= l_min <= l_max <= 32767 (the log-odds are int16).  The finalize entry
+ * points (dmf_fuse_finalize, dmf_fuse_finalize_device, dmf_fuse_finalize_slab_device,
+ * dmf_fuse_merge_finalize_device) return DMF_ERR_INVALID for any other clamp and touch
+ * neither the output nor the counters.  l_hit and l_miss are any int32 (the sum is formed
+ * in 64 bits). */
 typedef struct dmf_fuse_params {
   int32_t dmin_mm;  /* depth accepted iff dmin_mm <= d < dmax_mm */
   int32_t dmax_mm;

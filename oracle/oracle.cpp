@@ -1141,9 +1141,11 @@ int64_t orc_ogrid_download_reorganized(const orc_ogrid* g, int clean, float* out
   return m;
 }
 
-// Clamped fixed-point log-odds (milli-logit units) from the exact counts.
+// Clamped fixed-point log-odds (milli-logit units) from the exact counts.  A clamp outside
+// int16 or with l_min > l_max is rejected as by libdmf: out stays untouched.
 void orc_fuse_finalize(int64_t n, const int32_t* hits, const int32_t* misses, int l_hit, int l_miss,
                        int l_min, int l_max, int16_t* out) {
+  if (l_min > l_max || l_min < -32768 || l_max > 32767) return;
   for (int64_t i = 0; i < n; ++i) {
     int64_t L = (int64_t)hits[i] * l_hit + (int64_t)misses[i] * l_miss;
     if (L < l_min) L = l_min;

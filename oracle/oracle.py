@@ -392,6 +392,10 @@ def greedy_set_cover(sets, min_gain=5):
 
 
 def fuse_finalize(hits, misses, l_hit=847, l_miss=-405, l_min=-2000, l_max=3511):
+    """clamp(hits*l_hit + misses*l_miss, l_min, l_max) -> int16; the clamp bounds libdmf
+    rejects (l_min > l_max or outside int16) raise ValueError."""
+    if l_min > l_max or l_min < -32768 or l_max > 32767:
+        raise ValueError(f"log-odds clamp [{l_min}, {l_max}] must satisfy -32768 <= l_min <= l_max <= 32767")
     out = np.zeros(hits.size, np.int16)
     lib().orc_fuse_finalize(hits.size, np.ascontiguousarray(hits, np.int32),
                             np.ascontiguousarray(misses, np.int32), l_hit, l_miss, l_min, l_max, out)

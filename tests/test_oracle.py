@@ -368,3 +368,45 @@ def test_reverse_fast_centroid_is_narrowed_twice(oracle):
         eng.reverseRayTraceFast(v, T, True)
         seen[occluder] = int(v.voxel_table()[0][0])
     assert seen == {(55, 33, 68): 0, (55, 32, 68): 1}
+
+
+# (l_min, l_max) that every finalize implementation rejects: inverted, below
+# int16, above int16 -- where the kernel's clamp, the oracle's and numpy's clip would differ.
+BAD_CLAMPS = [(1, 0), (3511, -2000), (-32769, 0), (0, 32768), (-32769, 32768), (-(2 ** 31), 2 ** 31 - 1),
+              (32768, 32768), (-32769, -32769)]
+
+
+@pytest.mark.parametrize("l_min,l_max", BAD_CLAMPS)
+def test_fuse_finalize_rejects_invalid_clamp(oracle, l_min, l_max):
+    """oracle.fuse_finalize and dist.finalize_tiles_np raise ValueError for a clamp libdmf
+    rejects; the C entry orc_fuse_finalize returns with its output untouched."""
+    from dmf_amd import dist
+    h = np.array([0, 1, 5, -3, 2 ** 31 - 1, -(2 ** 31), 7, 9] * 2, np.int32)
+    m = h[::-1].copy()
+    with pytest.raises(ValueError):
+        oracle.fuse_finalize(h, m, 847, -405, l_min, l_max)
+    out = np.full(h.size, 12345, np.int16)
+    oracle.lib().orc_fuse_finalize(h.size, h, m, 847, -405, l_min, l_max, out)
+    assert (out == 12345).all()
+    with pytest.raises(ValueError):
+        dist.finalize_tiles_np(h, m, (2, 2, 4), 847, -405, l_min, l_max, out, 0, 1)
+    assert (out == 12345).all()
+
+
+@pytest.mark.parametrize("prm", [(847, -405, -2000, 3511), (32767, -32768, -32768, 32767), (-3, 5, 0, 0),
+                                 (7, 7, -7, -7), (2 ** 31 - 1, -(2 ** 31 - 1), -32768, 32767)])
+def test_fuse_finalize_accepts_the_int16_edges(oracle, prm):
+    """The widest valid clamp, degenerate (l_min == l_max) clamps and int32-edge coefficients
+    pass, and oracle.fuse_finalize equals int64 numpy arithmetic (as does finalize_tiles_np
+    over one 2x2x4 tile)."""
+    from dmf_amd import dist
+    rng = np.random.default_rng(5)
+    h = rng.integers(-(2 ** 31) + 1, 2 ** 31, 16).astype(np.int32)
+    m = rng.integers(-(2 ** 31) + 1, 2 ** 31, 16).astype(np.int32)
+    h[:4] = [0, 1, -1, 2 ** 31 - 1]
+    m[:4] = [0, -1, 2 ** 31 - 1, 2 ** 31 - 1]
+    ref = np.clip(h.astype(np.int64) * prm[0] + m.astype(np.int64) * prm[1], prm[2], prm[3]).astype(np.int16)
+    assert np.array_equal(oracle.fuse_finalize(h, m, *prm), ref)
+    out = np.zeros(16, np.int16)
+    dist.finalize_tiles_np(dist.to_tiled(h, (2, 2, 4), 16), dist.to_tiled(m, (2, 2, 4), 16), (2, 2, 4), *prm, out, 0, 1)
+    assert np.array_equal(out, ref)
