@@ -105,6 +105,26 @@ class RayTracingEngine {
     dmf_check(dmf_fuse_finalize(volume.handle(), acc.hits.data(), acc.misses.data(), &prm, out.data()));
     return out;
   }
+  // Extension: ray-cast of a fused log-odds grid (x-major int16, as logOdds
+  // returns it) from P poses -- per pixel the first cell with log-odds >= threshold along the
+  // fusion's probe ray of depth range_mm.  depth / cells are resized to P * height * width
+  // (row-major per pose): cells = getHashId of the surface cell or DMF_NO_CELL, depth =
+  // rayTraceVolume's value of that voxel or -1.  dmf_raycast_logodds in include/dmf.h.
+  void rayCastLogOdds(VoxelVolume& volume, const std::vector<int16_t>& logodds,
+                      const std::vector<Eigen::Affine3f>& poses, int threshold, int range_mm,
+                      std::vector<int32_t>& depth, std::vector<unsigned long long int>& cells) {
+    const size_t P = poses.size(), HW = (size_t)cam_.getHeight() * (size_t)cam_.getWidth();
+    const size_t n = (size_t)volume.xdim_ * volume.ydim_ * volume.zdim_;
+    if (logodds.size() != n) throw std::invalid_argument("rayCastLogOdds: logodds must hold xdim*ydim*zdim cells");
+    std::vector<float> p(12 * P);
+    for (size_t i = 0; i < P; ++i) dmf_compat::pose12(poses[i], &p[12 * i]);
+    depth.assign(P * HW, -1);
+    std::vector<uint64_t> h(P * HW, DMF_NO_CELL);
+    const dmf_camera c = cam_.abi();
+    dmf_check(dmf_raycast_logodds(volume.handle(), &c, logodds.data(), p.data(), (int32_t)P, threshold, range_mm,
+                                  depth.data(), h.data()));
+    cells.assign(h.begin(), h.end());
+  }
 
   // RayTracingEngine.hpp:229-264
   int rayTraceAndGetMinimum(VoxelVolume& volume, Eigen::Affine3f& T, int zdelta = 1, bool sparse = true) {

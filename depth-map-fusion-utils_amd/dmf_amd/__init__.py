@@ -28,6 +28,10 @@ from ._lib import DmfError, check, load, ptr
 
 __all__ = ["Camera", "VoxelVolume", "RayTracingEngine", "OccupancyGrid", "DmfError", "degree", "FuseParams"]
 
+# RayTracingEngine.raycast_logodds: the cell value of a pixel whose ray finds no solid cell
+# (DMF_NO_CELL, include/dmf.h; no getHashId is all ones)
+NO_CELL = np.uint64(0xFFFFFFFFFFFFFFFF)
+
 
 def degree(radian):
     """CommonUtilities.hpp:17 degree(): int((radian*180)/3.14159)."""
@@ -457,6 +461,27 @@ class RayTracingEngine:
         check(volume._L.dmf_fuse_finalize(volume._h, ptr(np.ascontiguousarray(hits, np.int32)),
                                           ptr(np.ascontiguousarray(misses, np.int32)), C.addressof(params), ptr(out)))
         return out
+
+    # ray-cast of a fused log-odds grid: predicted depth and first solid cell
+    def raycast_logodds(self, volume, logodds, poses, threshold=0, range_mm=1000):
+        """What a camera at each pose sees in the int16 log-odds grid `logodds` (xdim*ydim*zdim
+        cells, x-major, as fuse_finalize returns it): -> (depth (P, H, W) int32, cell (P, H, W)
+        uint64).  cell is the getHashId of the first cell with log-odds >= threshold along the
+        pixel's probe ray (the fusion's ray for depth range_mm), NO_CELL when there is none; depth
+        is rayTraceVolume's value of that voxel, -1 without one."""
+        poses = _poses(poses)
+        n = int(np.prod(volume.dims))
+        lo = np.asarray(logodds)
+        if lo.dtype != np.int16 or lo.size != n:
+            raise ValueError(f"logodds must be int16 with {n} cells (x-major over dims {tuple(volume.dims)}), "
+                             f"got {lo.dtype} with {lo.size}")
+        lo = np.ascontiguousarray(lo).reshape(-1)
+        P, H, W = poses.shape[0], self.cam_.height_, self.cam_.width_
+        depth = np.zeros((P, H, W), np.int32)
+        cell = np.zeros((P, H, W), np.uint64)
+        check(volume._L.dmf_raycast_logodds(volume._h, self._c(), ptr(lo), ptr(poses), P, int(threshold),
+                                            int(range_mm), ptr(depth), ptr(cell)))
+        return depth, cell
 
 
 def will_collide(volume, a, b):

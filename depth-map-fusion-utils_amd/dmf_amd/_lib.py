@@ -126,6 +126,8 @@ SIGNATURES = {
     "dmf_fuse_depth_device": (C.c_int, [_vp, _p, _p, _p, _i32, _p, _p, _p, _p]),
     "dmf_fuse_finalize": (C.c_int, [_vp, _p, _p, _p, _p]),
     "dmf_fuse_finalize_device": (C.c_int, [_vp, _p, _p, _p, _p]),
+    "dmf_raycast_logodds": (C.c_int, [_vp, _p, _p, _p, _i32, _i32, _i32, _p, _p]),
+    "dmf_raycast_logodds_device": (C.c_int, [_vp, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
     "dmf_fuse_counter_cells": (C.c_int, [_vp, _p]),
     "dmf_fuse_counters_to_linear_device": (C.c_int, [_vp, _p, _p]),
     "dmf_fuse_reserve": (C.c_int, [_vp, _p, _i32, C.c_uint64]),
@@ -219,7 +221,7 @@ def declared_symbols():
 FUSE_DEFAULT, FUSE_LDS_BOX, FUSE_CELL_WALK, FUSE_SLAB = 0, 31, 40, 57
 KNOBS = {"super_poses": 1, "pair_cap": 2, "batch_poses": 3, "part_max": 4, "span": 5, "tail_split": 6,
          "reverse_kernel": 7, "fwd_skip": 8, "a_hash": 9, "fault_inject": 10, "fwd_kernel": 11,
-         "bdist_cap": 12}
+         "bdist_cap": 12, "raycast_walk": 13}
 
 
 def fuse_status(vol):

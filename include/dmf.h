@@ -323,6 +323,30 @@ int dmf_fuse_finalize(dmf_volume* v, const int32_t* hits, const int32_t* misses,
 int dmf_fuse_finalize_device(dmf_volume* v, const int32_t* d_hits, const int32_t* d_misses,
                              const dmf_fuse_params* prm, int16_t* d_logodds);
 
+/* Ray-cast of a fused log-odds grid: what a camera at each of P poses sees in
+ * `logodds` (int16, x-major over xdim*ydim*zdim, as dmf_fuse_finalize* writes it).  Pixel (r, c)
+ * of pose p probes along exactly the ray the fusion traces for that pixel with depth range_mm
+ * (1..65535) and stops at the first cell of that ray's cell sequence with log-odds >= threshold
+ * (any int32).  Outputs, P*H*W each, either may be NULL:
+ *   cell   the surface cell's getHashId(x, y, z); DMF_NO_CELL when the ray finds none (decide
+ *          "no surface" from this: no hash is all ones);
+ *   depth  what rayTraceVolume gives that voxel, int(round(1000 * camera-frame z of its
+ *          centre)); -1 without a surface cell (a cell around the camera can legitimately have
+ *          depth <= 0).
+ * Only the volume's geometry is used, not its point-cloud occupancy, which the call leaves
+ * untouched.  The solid mask (L >= threshold) is rebuilt from the grid on every call.
+ * Host form: host pointers, synchronises.  Device form: device pointers, runs on the volume's
+ * stream without synchronising, allocates only when its scratch must grow; d_logodds may be the
+ * front of the merge's padded grid; d_stats (may be NULL): 2 counters += {rays that enter the
+ * grid, rays with a surface cell}.  Null v / cam / grid / poses, range_mm outside 1..65535 and
+ * P outside 1..65535 are DMF_ERR_INVALID; grids the fusion rejects are rejected alike. */
+#define DMF_NO_CELL UINT64_MAX
+int dmf_raycast_logodds(dmf_volume* v, const dmf_camera* cam, const int16_t* logodds, const float* poses,
+                        int32_t P, int32_t threshold, int32_t range_mm, int32_t* depth, uint64_t* cell);
+int dmf_raycast_logodds_device(dmf_volume* v, const dmf_camera* cam, const int16_t* d_logodds,
+                               const float* d_poses, int32_t P, int32_t threshold, int32_t range_mm,
+                               int32_t* d_depth, uint64_t* d_cell, uint64_t* d_stats);
+
 /* ---- multi-GPU merge over RCCL ------------------------
  * Poses shard across ranks, each rank fuses into its own replica of the counters, and
  * the replicas merge with integer collectives (bit-identical to one rank fusing all

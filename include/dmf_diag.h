@@ -58,7 +58,10 @@ enum dmf_knob {
                                 over units of 8x8 tiles (k_forward_q) */
   DMF_KNOB_BDIST_CAP = 12,   /* saturation of the brick distance field of the reverse / forward marches' empty-space
                                 jumps, in bricks (1..255; 0 = the default 63); rebuilt at the next march */
-  DMF_KNOB_COUNT = 13
+  DMF_KNOB_RAYCAST_WALK = 13, /* log-odds ray-cast (dmf_raycast_logodds*): 0 default, 1 the masked cell-by-cell walk,
+                                 2 the walk that jumps wholly empty 32^3 bricks and 8^3 tiles exactly; identical
+                                 outputs */
+  DMF_KNOB_COUNT = 14
 };
 int dmf_volume_set_knob(dmf_volume* v, int32_t knob, int64_t value);
 int dmf_volume_get_knob(const dmf_volume* v, int32_t knob, int64_t* value);
