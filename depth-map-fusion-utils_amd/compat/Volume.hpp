@@ -118,6 +118,36 @@ class VoxelVolume {
     return integrate(cloud, normals.get());
   }
 
+  // Surface of a fused log-odds grid (dmf_grid_surface; not in the reference): the
+  // cells with L >= occ that have a face neighbour with L <= free, in ascending getHashId, as
+  // voxel centres with normals towards free space.  The volume's occupancy is not touched.
+  void extractSurface(const std::vector<int16_t>& L, int occ, int free, std::vector<unsigned long long int>& cells,
+                      pcl::PointCloud<pcl::PointNormal>& out) {
+    if (L.size() != (size_t)xdim_ * ydim_ * zdim_) throw std::invalid_argument("extractSurface: grid size");
+    int64_t n = 0;
+    dmf_check(dmf_grid_surface(h_, L.data(), occ, free, nullptr, nullptr, nullptr, 0, &n, nullptr));
+    cells.assign((size_t)n, 0);
+    std::vector<float> xyz(3 * (size_t)n), nrm(3 * (size_t)n);
+    if (n)
+      dmf_check(dmf_grid_surface(h_, L.data(), occ, free, reinterpret_cast<uint64_t*>(cells.data()), xyz.data(),
+                                 nrm.data(), n, &n, nullptr));
+    out.points.resize((size_t)n);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+      pcl::PointNormal& p = out.points[i];
+      p.x = xyz[3 * i]; p.y = xyz[3 * i + 1]; p.z = xyz[3 * i + 2];
+      for (int k = 0; k < 3; ++k) p.normal[k] = nrm[3 * i + k];
+    }
+  }
+  // extractSurface's cloud into integratePointCloud(cloud, normals) without leaving the device:
+  // the number of surface cells.
+  long long integrateSurface(const std::vector<int16_t>& L, int occ, int free) {
+    if (L.size() != (size_t)xdim_ * ydim_ * zdim_) throw std::invalid_argument("integrateSurface: grid size");
+    int64_t n = 0;
+    dmf_check(dmf_volume_integrate_surface(h_, L.data(), occ, free, &n));
+    pull_occupied();
+    return (long long)n;
+  }
+
   // Volume.hpp:235-255 (with the reference's `i==j==k==0` test)
   std::vector<unsigned long long int> getNeighborHashes(unsigned long long int hash, int K = 1) {
     int x, y, z;
@@ -166,12 +196,16 @@ class VoxelVolume {
     }
     int64_t binned = 0, hazard = 0;
     dmf_check(dmf_volume_integrate(h_, xyz.data(), normals ? nrm.data() : nullptr, (int64_t)n, &binned, &hazard));
+    pull_occupied();
+    return true;
+  }
+
+  void pull_occupied() {
     int64_t V = 0;
     dmf_check(dmf_volume_occupied(h_, nullptr, 0, &V));
     occupied_cells_.resize((size_t)V);
     if (V) dmf_check(dmf_volume_occupied(h_, reinterpret_cast<uint64_t*>(occupied_cells_.data()), V, &V));
     touch();
-    return true;
   }
 
   void rebuild_mirror() {

@@ -62,7 +62,10 @@ enum ScratchSlot {
   kScOgP0, kScOgP1, kScOgFinal, kScOgOcc,  // OccupancyGrid reorganization (dmf_ogrid.hip)
   kScRevItems,  // reverseRayTraceFast's item-ordered (spatial order) result masks (dmf_trace.hip)
   kScBkOvf, kScBkOvf1,  // pass A's hashed-histogram overflow lists, per staging slot (dmf_fuse.hip)
-  kScRcFine, kScRcCoarse  // the log-odds ray-cast's solid mask and its tile + brick levels (dmf_fuse.hip)
+  kScRcFine, kScRcCoarse,  // the log-odds ray-cast's solid mask and its tile + brick levels (dmf_fuse.hip)
+  // surface extraction (dmf_surface.hip): the solid, free and surface masks, the per-row counts
+  // and their scan, the {surface, solid} counters, and the host forms' output staging
+  kScSfSolid, kScSfFree, kScSfSurf, kScSfCounts, kScSfBases, kScSfTotals, kScSfHash, kScSfXyz, kScSfNrm
 };
 
 // Striped statistics: kernels add into slot (block % kStatSlots) of a zeroed buffer

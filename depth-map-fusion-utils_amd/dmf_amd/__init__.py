@@ -222,6 +222,40 @@ class VoxelVolume:
     def integrate_device(self, d_xyz, d_normals, n):
         check(self._L.dmf_volume_integrate_device(self._h, d_xyz, d_normals, int(n)))
 
+    # -- surface of a fused log-odds grid, on the GPU
+    def _logodds(self, logodds):
+        n = int(np.prod(self.dims))
+        lo = np.asarray(logodds)
+        if lo.dtype != np.int16 or lo.size != n:
+            raise ValueError(f"logodds must be int16 with {n} cells (x-major over dims {tuple(self.dims)}), "
+                             f"got {lo.dtype} with {lo.size}")
+        return np.ascontiguousarray(lo).reshape(-1)
+
+    def extract_surface(self, logodds, occ_threshold=1, free_threshold=-1):
+        """The surface cells of the int16 log-odds grid `logodds` (xdim*ydim*zdim cells, x-major, as
+        fuse_finalize returns it) -> (hash uint64 (n,), xyz float32 (n, 3), normals float32 (n, 3)),
+        in ascending getHashId: the cells with log-odds >= occ_threshold that have a face neighbour
+        with log-odds <= free_threshold, their voxel centres and normals towards free space.  The
+        volume's point-cloud occupancy is not touched."""
+        lo = self._logodds(logodds)
+        n = C.c_int64(0)
+        args = (self._h, ptr(lo), int(occ_threshold), int(free_threshold))
+        check(self._L.dmf_grid_surface(*args, None, None, None, 0, C.addressof(n), None))
+        m = n.value
+        h, xyz, nrm = np.zeros(m, np.uint64), np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32)
+        if m:
+            check(self._L.dmf_grid_surface(*args, ptr(h), ptr(xyz), ptr(nrm), m, C.addressof(n), None))
+        return h, xyz, nrm
+
+    def integrate_surface(self, logodds, occ_threshold=1, free_threshold=-1):
+        """integratePointCloud(cloud, normals) of extract_surface's cloud without leaving the
+        device -> the number of surface cells."""
+        lo = self._logodds(logodds)
+        n = C.c_int64(0)
+        check(self._L.dmf_volume_integrate_surface(self._h, ptr(lo), int(occ_threshold), int(free_threshold),
+                                                   C.addressof(n)))
+        return n.value
+
     @property
     def occupied_cells_(self):
         n = C.c_int64(0)

@@ -347,6 +347,40 @@ int dmf_raycast_logodds_device(dmf_volume* v, const dmf_camera* cam, const int16
                                const float* d_poses, int32_t P, int32_t threshold, int32_t range_mm,
                                int32_t* d_depth, uint64_t* d_cell, uint64_t* d_stats);
 
+/* Surface of a fused log-odds grid as an oriented cloud, in order: the cloud
+ * that integratePointCloud(cloud, normals) (Volume.hpp:199-228) takes, from `logodds` (int16,
+ * x-major over xdim*ydim*zdim, as dmf_fuse_finalize* writes it).  A cell is solid iff its
+ * log-odds >= occ_threshold and free iff it lies in the grid with log-odds <= free_threshold
+ * (any int32 pair; a neighbour outside the grid reads as 0 and is never free).  A surface cell
+ * is a solid cell with a free face neighbour (6-neighbourhood).  Per surface cell, in ascending
+ * getHashId (Volume.hpp:143-148; the x-major order in which a scan of voxels_[x][y][z] would
+ * insert them), each output may be NULL:
+ *   hash     getHashId(x, y, z);
+ *   xyz      3 floats: the voxel centre as reverseRayTraceFast forms it from the index
+ *            (RayTracingEngine.hpp:151-157): x = float(i * delta + min), centre = float(x + delta / 2);
+ *   normals  3 floats towards free space: g_a = N(c - e_a) - N(c + e_a) over the face neighbours'
+ *            log-odds (outside the grid: 0), n = float(g) / sqrtf(gx*gx + (gy*gy + gz*gz)) in
+ *            float32 (Eigen's normalized()); (0, 0, 0) when g = 0.
+ * Counts are {surface cells, solid cells} of the whole grid, whatever the capacity.  Only the
+ * volume's geometry is used; its point-cloud occupancy is neither read nor changed.
+ * Device form: device pointers, only enqueues on the volume's stream, allocates only when its
+ * scratch must grow; writes the first min(count, cap) entries and nothing at or past cap, and
+ * always d_count[2] (compare d_count[0] with cap).  Host form: host pointers, synchronises;
+ * cap < count is DMF_ERR_CAPACITY with *n = the need and the outputs untouched, except that
+ * cap = 0 with NULL outputs is the size query (DMF_OK); n and n_solid may be NULL.
+ * dmf_volume_integrate_surface extracts on the device and hands xyz and normals to
+ * integratePointCloud(cloud, normals) there: after the upload of the grid only the count (*n,
+ * may be NULL) comes back.  Null v / grid, a negative cap and, in the device form, a null
+ * d_count or three null outputs are DMF_ERR_INVALID; an unconstructed volume is DMF_ERR_STATE;
+ * more than 2048 cells on an axis is DMF_ERR_RANGE. */
+int dmf_grid_surface_device(dmf_volume* v, const int16_t* d_logodds, int32_t occ_threshold,
+                            int32_t free_threshold, uint64_t* d_hash, float* d_xyz, float* d_normals,
+                            int64_t cap, uint64_t* d_count);
+int dmf_grid_surface(dmf_volume* v, const int16_t* logodds, int32_t occ_threshold, int32_t free_threshold,
+                     uint64_t* hash, float* xyz, float* normals, int64_t cap, int64_t* n, int64_t* n_solid);
+int dmf_volume_integrate_surface(dmf_volume* v, const int16_t* logodds, int32_t occ_threshold,
+                                 int32_t free_threshold, int64_t* n);
+
 /* ---- multi-GPU merge over RCCL ------------------------
  * Poses shard across ranks, each rank fuses into its own replica of the counters, and
  * the replicas merge with integer collectives (bit-identical to one rank fusing all
