@@ -95,6 +95,44 @@ class RayTracingEngine {
     acc.hit_rays += st[2];
     return acc;
   }
+  // Extension: the same fusion of point clouds with sensor origins, the
+  // insertPointCloud(scan, origin) call.  xyz: S scans of N world-frame endpoints each (packed
+  // x, y, z), origins: the S world-frame sensor positions (S = origins.size() / 3).  Point i of
+  // scan s is the ray origins[s] -> xyz[s][i], traced exactly as fuseDepth traces a pixel's.  A
+  // point with a non-finite coordinate is no ray (pad scans of unequal length with NaN); there is
+  // no range gate (params' dmin_mm / dmax_mm are not applied).  dmf_fuse_points in include/dmf.h.
+  FusionCounts& fusePoints(VoxelVolume& volume, const std::vector<float>& xyz, const std::vector<float>& origins,
+                           FusionCounts& acc, const dmf_fuse_params* params = nullptr) {
+    const size_t S = origins.size() / 3;
+    if (S == 0 || origins.size() != 3 * S || xyz.size() % (3 * S) != 0)
+      throw std::invalid_argument("fusePoints: origins must hold S x 3 floats and xyz S scans of N x 3 floats");
+    const size_t N = xyz.size() / (3 * S);
+    const size_t n = (size_t)volume.xdim_ * volume.ydim_ * volume.zdim_;
+    if (acc.hits.size() != n) acc.hits.assign(n, 0);
+    if (acc.misses.size() != n) acc.misses.assign(n, 0);
+    dmf_fuse_params prm;
+    dmf_fuse_params_default(&prm);
+    if (params) prm = *params;
+    int64_t st[3] = {0, 0, 0};
+    dmf_check(dmf_fuse_points(volume.handle(), xyz.data(), origins.data(), (int32_t)S, (int64_t)N, &prm,
+                              acc.hits.data(), acc.misses.data(), st));
+    acc.updates += st[0];
+    acc.rays += st[1];
+    acc.hit_rays += st[2];
+    return acc;
+  }
+  // One cloud as readPointCloud yields it (FileRoutines.hpp), seen from one sensor position.
+  FusionCounts& fusePoints(VoxelVolume& volume, const pcl::PointCloud<pcl::PointXYZRGBNormal>::Ptr& cloud,
+                           const Eigen::Vector3f& origin, FusionCounts& acc, const dmf_fuse_params* params = nullptr) {
+    std::vector<float> xyz;
+    xyz.reserve(3 * cloud->points.size());
+    for (const auto& p : cloud->points) {
+      xyz.push_back(p.x);
+      xyz.push_back(p.y);
+      xyz.push_back(p.z);
+    }
+    return fusePoints(volume, xyz, std::vector<float>{origin(0), origin(1), origin(2)}, acc, params);
+  }
   // The clamped int16 log-odds grid of fused counts (x-major): clamp(hits * l_hit + misses *
   // l_miss, l_min, l_max) milli-logit (dmf_fuse_finalize).
   std::vector<int16_t> logOdds(VoxelVolume& volume, const FusionCounts& acc, const dmf_fuse_params* params = nullptr) {

@@ -11,7 +11,10 @@
 //   - (extension, BASELINE.json north_star) with depth.bin: the first P poses' 640x480
 //     uint16 depth frames fused by RayTracingEngine::fuseDepth (3D-DDA log-odds), the
 //     counts and log-odds written to out.bin (int32 hits | int32 misses | int16 log-odds).
-// usage: raytracing_headless cloud.bin poses.txt [depth.bin P out.bin]
+//   - (extension) with points.bin: S scans of N float32 x y z points fused by
+//     RayTracingEngine::fusePoints from the first S poses' camera centres, the counts written to
+//     pout.bin (int32 hits | int32 misses); scan 0 again through the point-cloud overload.
+// usage: raytracing_headless cloud.bin poses.txt [depth.bin P out.bin [points.bin S N pout.bin]]
 #include <algorithm>
 #include <cstdio>
 #include <fstream>
@@ -157,6 +160,35 @@ int main(int argc, char** argv) {
     o.write(reinterpret_cast<const char*>(acc.hits.data()), (streamsize)(acc.hits.size() * sizeof(int32_t)));
     o.write(reinterpret_cast<const char*>(acc.misses.data()), (streamsize)(acc.misses.size() * sizeof(int32_t)));
     o.write(reinterpret_cast<const char*>(lo.data()), (streamsize)(lo.size() * sizeof(int16_t)));
+  }
+  if (argc >= 10) {  // fusion of S scans of N points, seen from the first S poses' camera centres
+    const size_t S = (size_t)stoi(argv[7]), N = (size_t)stoi(argv[8]);
+    vector<float> xyz(S * N * 3), origins;
+    ifstream f(argv[6], ios::binary);
+    if (!f.read(reinterpret_cast<char*>(xyz.data()), (streamsize)(xyz.size() * sizeof(float)))) {
+      cerr << "short points file\n";
+      return 3;
+    }
+    for (size_t s = 0; s < S; ++s)
+      for (int j = 0; j < 3; ++j) origins.push_back(camera_locations[s](j, 3));
+    RayTracingEngine::FusionCounts acc;
+    engine.fusePoints(volume, xyz, origins, acc);
+    cout << "points " << acc.updates << " " << acc.rays << " " << acc.hit_rays << "\n";
+    ofstream o(argv[9], ios::binary);
+    o.write(reinterpret_cast<const char*>(acc.hits.data()), (streamsize)(acc.hits.size() * sizeof(int32_t)));
+    o.write(reinterpret_cast<const char*>(acc.misses.data()), (streamsize)(acc.misses.size() * sizeof(int32_t)));
+    // scan 0 again as the cloud readPointCloud would yield, with one origin
+    pcl::PointCloud<pcl::PointXYZRGBNormal>::Ptr scan(new pcl::PointCloud<pcl::PointXYZRGBNormal>);
+    for (size_t i = 0; i < N; ++i) {
+      pcl::PointXYZRGBNormal p;
+      p.x = xyz[3 * i]; p.y = xyz[3 * i + 1]; p.z = xyz[3 * i + 2];
+      scan->points.push_back(p);
+    }
+    Eigen::Vector3f origin;
+    origin << origins[0], origins[1], origins[2];
+    RayTracingEngine::FusionCounts one;
+    engine.fusePoints(volume, scan, origin, one);
+    cout << "points_scan0 " << one.updates << " " << one.rays << " " << one.hit_rays << "\n";
   }
   return 0;
 }

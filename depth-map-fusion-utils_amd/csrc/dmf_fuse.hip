@@ -252,6 +252,103 @@ __device__ inline int pixel_depth(const CamP& cam, const uint16_t* __restrict__ 
   return (r >= cam.H || c >= cam.W) ? -1 : (int)depth[((int64_t)p * cam.H + r) * cam.W + c];
 }
 
+// ---- ray sources.  The fusion kernels that make rays (k_fuse_l, pass A of the
+// brick pipeline) take their rays from a source type: DepthSrc, the pixels of P depth frames
+// behind a pinhole camera, or PointSrc, S scans of N world-frame endpoints with one sensor
+// origin per scan.  A source names a frame (pose or scan) and, in it, 64-ray packets; per
+// workgroup it loads the frame (`begin`: the grid coordinates of the ray origin, once), per lane
+// a sample (`load`) and from it the §4 ray (`quant` up to the quantised endpoints, `ray` up to
+// the walk state).  `valid` = the sample is a ray (statistics counter 1), whether or not it
+// meets the grid.  Everything after the ray record is the same code for both.
+struct DepthSrc {
+  CamP cam;
+  const uint16_t* depth;
+  const PoseX* poses;
+  int dmin, dmax, packets_x;
+  struct Frame { float Tf[12]; };
+  struct Sample { int d, r, c; };
+  // the workgroup's pose, held in registers (read in the packet loop, it was reloaded after
+  // every packet's record stores, which might alias it: ±0, profiles/r06i -- as the next
+  // packet's depth loaded a packet ahead, +5 % A, pass A is not waiting on its stores)
+  __device__ void begin(const Geom& g, int p, Frame& f, double go[3]) const {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) f.Tf[i] = poses[p].f[i];
+    const float O[3] = {f.Tf[3], f.Tf[7], f.Tf[11]};
+    grid_origin(g, O, go);
+  }
+  __device__ Sample load(int p, int q, int l) const {
+    Sample s;
+    s.r = (q / packets_x) * 8 + (l >> 3);
+    s.c = (q % packets_x) * 8 + (l & 7);
+    s.d = pixel_depth(cam, depth, p, s.r, s.c);
+    return s;
+  }
+  __device__ bool quant(const Geom& g, const Frame& f, const double go[3], const Sample& s, int64_t qs[3],
+                        int64_t qe[3], bool& inside, bool& valid) const {
+    return pixel_quant_go(g, cam, s.d, f.Tf, go, s.r, s.c, dmin, dmax, qs, qe, inside, valid);
+  }
+  __device__ int ray(const Geom& g, int p, int q, int l, Ray& R, bool& valid) const {
+    return pixel_ray(g, cam, depth, poses, p, (q / packets_x) * 8 + (l >> 3), (q % packets_x) * 8 + (l & 7), dmin,
+                     dmax, R, valid);
+  }
+};
+
+// Point i of scan s is ray index s * ceil(N / 64) * 64 + i: 64 consecutive points are one
+// packet, the lanes past N of a scan's last packet are no rays.  A lane loads its endpoint as
+// three dwords at stride 12 (a wave reads 768 contiguous bytes).  A point with a non-finite
+// coordinate is no ray, and neither is any point of a scan whose origin has one.  There is no
+// depth value, so no range gate.
+struct PointSrc {
+  const float* xyz;      // [S][N][3]
+  const float* origins;  // [S][3]
+  int64_t N;
+  struct Frame { bool live; };
+  struct Sample { float E[3]; bool ok; };
+  __device__ static bool finite3(const float v[3]) {
+    return __builtin_isfinite(v[0]) & __builtin_isfinite(v[1]) & __builtin_isfinite(v[2]);
+  }
+  __device__ void origin(int p, float O[3]) const {
+    const float* const o = origins + 3 * (int64_t)p;
+    O[0] = o[0];
+    O[1] = o[1];
+    O[2] = o[2];
+  }
+  __device__ void begin(const Geom& g, int p, Frame& f, double go[3]) const {
+    float O[3];
+    origin(p, O);
+    f.live = finite3(O);
+    grid_origin(g, O, go);
+  }
+  __device__ Sample load(int p, int q, int l) const {
+    Sample s;
+    const int64_t i = (int64_t)q * 64 + l;
+    s.ok = i < N;
+    const float* const e = xyz + ((int64_t)p * N + (s.ok ? i : 0)) * 3;
+    s.E[0] = e[0];
+    s.E[1] = e[1];
+    s.E[2] = e[2];
+    return s;
+  }
+  __device__ bool quant(const Geom& g, const Frame& f, const double go[3], const Sample& s, int64_t qs[3],
+                        int64_t qe[3], bool& inside, bool& valid) const {
+    inside = false;
+    valid = f.live & s.ok & finite3(s.E);
+    if (!valid) return false;
+    inside = endpoint_inside(g, s.E);
+    return dda_quantize_go(g, go, s.E, inside, qs, qe);
+  }
+  __device__ int ray(const Geom& g, int p, int q, int l, Ray& R, bool& valid) const {
+    float O[3];
+    origin(p, O);
+    const Sample s = load(p, q, l);
+    R.left = 0;
+    valid = finite3(O) && s.ok && finite3(s.E);
+    if (!valid) return 0;
+    if (!dda_setup(g, O, s.E, endpoint_inside(g, s.E), R)) { R.left = 0; return 0; }
+    return R.left;
+  }
+};
+
 __device__ inline void wave_stats(unsigned long long* stats, unsigned long long upd, unsigned long long ray,
                                   unsigned long long hit) {
   for (int o = 32; o > 0; o >>= 1) {
@@ -302,8 +399,8 @@ __device__ inline int small_div(int i, int b, float rb, int& rem) {
 __device__ inline int popc(uint32_t v) { return __builtin_popcount(v); }
 __device__ inline int popc(uint64_t v) { return __builtin_popcountll(v); }
 
-// Production fusion kernel.  One 64-lane workgroup per 8x8 pixel
-// packet of one frame; the wave runs its own rounds (no cross-wave barriers).  Per
+// Production fusion kernel.  One 64-lane workgroup per 64-ray packet of one
+// frame of the ray source (DepthSrc: an 8x8 pixel packet; PointSrc: 64 consecutive points); the wave runs its own rounds (no cross-wave barriers).  Per
 // round of kS cell updates per ray:
 //  1. walk: kS unconditional exact-DDA steps (dda_select, ties x < y < z), recording
 //     2-bit axis codes.  A lane with fewer advances finishes in this round (or has
@@ -325,10 +422,9 @@ __device__ inline int popc(uint64_t v) { return __builtin_popcountll(v); }
 //     (tools/sim_fusion_flush_order.py; tile order: 4.85), which is one memory-side request.
 // A round whose box exceeds kBox cells adds its misses to HBM directly.  Hits (one per
 // ray) go straight to HBM.  Counts are exact integers: bit-identical to the oracle.
-template <int kS, int kBox>
-__global__ __launch_bounds__(64) void k_fuse_l(Geom g, CamP cam, const uint16_t* __restrict__ depth,
-                                               const PoseX* __restrict__ poses, int dmin, int dmax, int packets_x,
-                                               int32_t* __restrict__ hits, int32_t* __restrict__ misses,
+template <int kS, int kBox, class Src>
+__global__ __launch_bounds__(64) void k_fuse_l(Geom g, Src src, int32_t* __restrict__ hits,
+                                               int32_t* __restrict__ misses,
                                                unsigned long long* __restrict__ stats) {
   static_assert(kS <= 31, "2-bit codes of up to 31 advances with a 64-bit field mask");
   using CodeT = typename std::conditional<(kS <= 15), uint32_t, uint64_t>::type;
@@ -341,11 +437,9 @@ __global__ __launch_bounds__(64) void k_fuse_l(Geom g, CamP cam, const uint16_t*
   const int l = threadIdx.x;
   for (int i = l; i < kBox; i += 64) box[i] = 0;
   const Tiles tl = tiles_of(g.n);
-  const int pr = (blockIdx.x / packets_x) * 8 + (l >> 3), pc = (blockIdx.x % packets_x) * 8 + (l & 7);
   Ray R;
   bool valid;
-  const unsigned long long upd = (unsigned long long)pixel_ray(g, cam, depth, poses, blockIdx.y, pr, pc, dmin, dmax,
-                                                               R, valid);
+  const unsigned long long upd = (unsigned long long)src.ray(g, (int)blockIdx.y, (int)blockIdx.x, l, R, valid);
   const unsigned long long nvalid = valid ? 1 : 0, nhit = (R.left > 0 && R.end_inside) ? 1 : 0;
   int32_t E01 = R.E01, E02 = R.E02, E12 = R.E12;
   const int32_t K0 = R.K[0], K1 = R.K[1], K2 = R.K[2];
@@ -627,12 +721,11 @@ __device__ inline void hash_add_first(uint32_t* tab, uint32_t mask, int shift, i
   if (!hash_add(tab, mask, shift, (uint32_t)b, n)) *ovf = 1u;
 }
 
+template <class Src>
 struct BkRaysArgs {
   Geom g;
-  CamP cam;
-  const uint16_t* depth;
-  const PoseX* poses;
-  int dmin, dmax, packets_x, packets_pose, wg_pose, span;
+  Src src;  // the ray source (DepthSrc or PointSrc) of the super-batch
+  int packets_pose, wg_pose, span;
   BkGeom bg;
   ulonglong2* rays;
   uint64_t* paths;
@@ -646,9 +739,9 @@ struct BkRaysArgs {
   int hash_log;    // log2 of the hashed histogram's words (HASH)
 };
 
-// Pass A for workgroup wg.  Workgroup = 4 (or 16) waves over a span of 8x8 packets of ONE
-// pose (wg_pose workgroups per pose, the last one of a pose shorter); ray index = packet * 64
-// + lane.  Counts are kept per (pose, brick): pose_cnt[p][b] (the workgroup's base inside
+// Pass A for workgroup wg.  Workgroup = 4 (or 16) waves over a span of 64-ray packets (DepthSrc:
+// 8x8 pixels) of ONE pose, or one scan of a PointSrc ("pose" below stands for either; wg_pose
+// workgroups per pose, the last one of a pose shorter); ray index = packet * 64 + lane.  Counts are kept per (pose, brick): pose_cnt[p][b] (the workgroup's base inside
 // that count is wg_base[wg][b]) and per pose: pose_pairs[p], so that the device can cut the
 // call into pose batches by the pairs they really make (k_bk_batches) and any batch's
 // per-brick lists can be laid out (k_bk_batch_counts) without re-running this pass.
@@ -658,8 +751,8 @@ struct BkRaysArgs {
 // (DESIGN.md §5.10).  HASH: the hashed histogram above; a workgroup whose table overflows
 // writes only its ray records, lists itself in ovl and leaves counts and statistics to
 // k_bk_rays_recover.  sh: two shared words (touched-list count, overflow flag).
-template <bool H16, bool HASH>
-__device__ inline void bk_rays_wg(const BkRaysArgs& A_, unsigned wg, uint32_t* hist, uint32_t* sh) {
+template <bool H16, bool HASH, class Src>
+__device__ inline void bk_rays_wg(const BkRaysArgs<Src>& A_, unsigned wg, uint32_t* hist, uint32_t* sh) {
   const Geom& g = A_.g;
   const BkGeom& bg = A_.bg;
   unsigned long long* const stats = stat_slot(A_.stats);
@@ -683,28 +776,19 @@ __device__ inline void bk_rays_wg(const BkRaysArgs& A_, unsigned wg, uint32_t* h
   unsigned long long upd = 0, nvalid = 0, nhit = 0;
   // (loading the next packet's depth one packet ahead measured slower: 0.79 -> 0.84 ms)
   double go[3];
-  // the workgroup's pose, held in registers (read in the packet loop, it was reloaded after
-  // every packet's record stores, which might alias it: ±0, profiles/r06i -- as the next
-  // packet's depth loaded a packet ahead, +5 % A, pass A is not waiting on its stores)
-  float Tf[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) Tf[i] = A_.poses[pw].f[i];
-  {
-    const float O[3] = {Tf[3], Tf[7], Tf[11]};
-    grid_origin(g, O, go);
-  }
+  typename Src::Frame fr;  // the workgroup's frame (DepthSrc: its pose, held in registers)
+  A_.src.begin(g, pw, fr, go);
   for (int64_t pk = pk0 + w; pk < pk1; pk += nw) {
     const int p = pw;
     const int q = (int)(pk - (int64_t)p * A_.packets_pose);
-    const int r = (q / A_.packets_x) * 8 + (l >> 3), c = (q % A_.packets_x) * 8 + (l & 7);
-    const int d = pixel_depth(A_.cam, A_.depth, p, r, c);
+    const typename Src::Sample sm = A_.src.load(p, q, l);
     int64_t qs[3], qe[3];
     bool inside, valid;
     ulonglong2 rec;
     rec.x = 0;
     rec.y = 0;
     uint64_t path = 0;  // the crossing axes of the coarse walk (pass B replays them)
-    if (pixel_quant_go(g, A_.cam, d, Tf, go, r, c, A_.dmin, A_.dmax, qs, qe, inside, valid)) {
+    if (A_.src.quant(g, fr, go, sm, qs, qe, inside, valid)) {
       uint64_t A, B;
       bk::pack_ray(qs, qe, inside, A, B);
       rec.x = A;
@@ -776,15 +860,16 @@ __device__ inline void bk_rays_wg(const BkRaysArgs& A_, unsigned wg, uint32_t* h
   if (stats) wave_stats(stats, upd, nvalid, nhit);
 }
 
-template <bool H16>
-__global__ __launch_bounds__(kBkPassThreadsBig) void k_bk_rays(BkRaysArgs a) {
+template <bool H16, class Src>
+__global__ __launch_bounds__(kBkPassThreadsBig) void k_bk_rays(BkRaysArgs<Src> a) {
   extern __shared__ uint32_t hist[];
   __shared__ uint32_t sh[2];
   bk_rays_wg<H16, false>(a, blockIdx.x, hist, sh);
 }
 
 // Pass A with the hashed histogram (256-lane workgroups, 8 KB of LDS by default).
-__global__ __launch_bounds__(kBkPassThreads) void k_bk_rays_hash(BkRaysArgs a) {
+template <class Src>
+__global__ __launch_bounds__(kBkPassThreads) void k_bk_rays_hash(BkRaysArgs<Src> a) {
   extern __shared__ uint32_t tab[];
   __shared__ uint32_t sh[2];
   bk_rays_wg<true, true>(a, blockIdx.x, tab, sh);
@@ -792,7 +877,8 @@ __global__ __launch_bounds__(kBkPassThreads) void k_bk_rays_hash(BkRaysArgs a) {
 
 // The workgroups whose hashed histogram overflowed, redone with the direct 16-bit table
 // (persistent: the grid strides over the list; exits at once when it is empty).
-__global__ __launch_bounds__(kBkPassThreadsBig) void k_bk_rays_recover(BkRaysArgs a) {
+template <class Src>
+__global__ __launch_bounds__(kBkPassThreadsBig) void k_bk_rays_recover(BkRaysArgs<Src> a) {
   extern __shared__ uint32_t hist[];
   __shared__ uint32_t sh[2];
   const uint32_t n = a.ovl[0];
@@ -2115,8 +2201,7 @@ static int cu_count(int device) {
 
 struct BkPlan {
   BkGeom bg;
-  int pkx = 0, pky = 0;
-  int64_t ppose = 0;          // 8x8 packets per pose
+  int64_t ppose = 0;          // 64-ray packets per pose (or per scan of points)
   int64_t max_pairs_ray = 0;  // geometric bound of (ray, brick) pairs per ray
   int64_t PS = 0;             // poses per super-batch (one pass A over all of them)
   int64_t PBg = 0;            // poses per batch under the geometric bound (>= 1)
@@ -2136,12 +2221,15 @@ struct BkPlan {
   size_t max_parts() const { return (size_t)bg.nbricks + pair_cap / part_max + 1 + 3 * 1024; }
 };
 
-static int bk_plan(const dmf_volume* v, const CamP& cp, const Geom& g, int P, BkPlan& pl) {
+// 64-ray packets per frame of a ray source: 8x8 pixel packets of a camera, ceil(N / 64) of a scan
+static int64_t cam_packets(const CamP& cp) { return (int64_t)((cp.W + 7) / 8) * ((cp.H + 7) / 8); }
+static int64_t scan_packets(int64_t N) { return (N + 63) / 64; }
+
+// `ppose` = packets per pose (cam_packets) or per scan (scan_packets); P = poses or scans
+static int bk_plan(const dmf_volume* v, int64_t ppose, const Geom& g, int P, BkPlan& pl) {
   const int64_t* kn = v->knob;
   pl.bg = brick_geom(g);
-  pl.pkx = (cp.W + 7) / 8;
-  pl.pky = (cp.H + 7) / 8;
-  pl.ppose = (int64_t)pl.pkx * pl.pky;
+  pl.ppose = ppose;
   pl.max_pairs_ray = 1 + (pl.bg.nb[0] - 1) + (pl.bg.nb[1] - 1) + (pl.bg.nb[2] - 1);
   pl.rec_bytes = v->fuse_variant == DMF_FUSE_CELL_WALK ? 24 : 20;
   const int64_t rays_pose = pl.ppose * 64;
@@ -2215,9 +2303,12 @@ static int bk_attributes() {
   static std::atomic<bool> attr_set{false};
   if (!attr_set.load()) {
     const int lds = (int)(sizeof(uint32_t) * 32768);
-    DMF_HIP(hipFuncSetAttribute((const void*)k_bk_rays<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    DMF_HIP(hipFuncSetAttribute((const void*)k_bk_rays_recover, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    DMF_HIP(hipFuncSetAttribute((const void*)k_bk_rays_hash, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    DMF_HIP(hipFuncSetAttribute((const void*)k_bk_rays<true, DepthSrc>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    DMF_HIP(hipFuncSetAttribute((const void*)k_bk_rays_recover<DepthSrc>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    DMF_HIP(hipFuncSetAttribute((const void*)k_bk_rays_hash<DepthSrc>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    DMF_HIP(hipFuncSetAttribute((const void*)k_bk_rays<true, PointSrc>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    DMF_HIP(hipFuncSetAttribute((const void*)k_bk_rays_recover<PointSrc>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    DMF_HIP(hipFuncSetAttribute((const void*)k_bk_rays_hash<PointSrc>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     DMF_HIP(hipFuncSetAttribute((const void*)k_bk_pairs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     DMF_HIP(hipFuncSetAttribute((const void*)k_bk_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     attr_set.store(true);
@@ -2347,11 +2438,48 @@ static int fault_words(dmf_volume* v) {
   return DMF_OK;
 }
 
-static int fuse_bricks(dmf_volume* v, const CamP& cp, const Geom& g, const uint16_t* d_depth, const PoseX* tab,
-                       const float* d_poses, int P, const dmf_fuse_params* prm, int32_t* d_hits, int32_t* d_misses,
+// The host side of a ray source: the frames of one call, and the device source of the
+// super-batch of frames [s0, s0 + ps) as pass A reads it on stream sa.
+struct DepthFeed {
+  using Src = DepthSrc;
+  CamP cp;
+  const uint16_t* d_depth;
+  const PoseX* tab;       // the call's pose table (serial calls)
+  const float* d_poses;   // the caller's poses (staged calls build the slot's table from them)
+  int dmin, dmax;
+  int64_t packets() const { return cam_packets(cp); }
+  int source(dmf_volume* v, int64_t s0, int64_t ps, int64_t PS, bool staged, int slot, hipStream_t sa, Src& out) const {
+    const PoseX* tab_a = tab + s0;
+    if (staged) {
+      void* t;
+      DMF_TRY(scratch(v, slot ? kScStPoses1 : kScStPoses0, sizeof(PoseX) * (size_t)PS, &t));
+      DMF_TRY(pose_table_into(d_poses + (size_t)s0 * 12, (int)ps, (PoseX*)t, sa));
+      tab_a = (const PoseX*)t;
+    }
+    out = Src{cp, d_depth + (size_t)s0 * cp.H * cp.W, tab_a, dmin, dmax, (cp.W + 7) / 8};
+    return DMF_OK;
+  }
+};
+// Points: the scans' origins take the pose table's place, read as the caller wrote them (a
+// staged pass A follows the input stream as it does for depth frames).
+struct PointFeed {
+  using Src = PointSrc;
+  const float* d_xyz;
+  const float* d_origins;
+  int64_t N;
+  int64_t packets() const { return scan_packets(N); }
+  int source(dmf_volume*, int64_t s0, int64_t, int64_t, bool, int, hipStream_t, Src& out) const {
+    out = Src{d_xyz + (size_t)s0 * (size_t)N * 3, d_origins + (size_t)s0 * 3, N};
+    return DMF_OK;
+  }
+};
+
+template <class Feed>
+static int fuse_bricks(dmf_volume* v, const Feed& feed, const Geom& g, int P, int32_t* d_hits, int32_t* d_misses,
                        unsigned long long* st, uint64_t* d_user, bool staged, bool capturing) {
+  using Src = typename Feed::Src;
   BkPlan pl;
-  DMF_TRY(bk_plan(v, cp, g, P, pl));
+  DMF_TRY(bk_plan(v, feed.packets(), g, P, pl));
   const BkGeom& bg = pl.bg;
   DMF_TRY(bk_attributes());
   DMF_TRY(fault_words(v));
@@ -2378,17 +2506,16 @@ static int fuse_bricks(dmf_volume* v, const CamP& cp, const Geom& g, const uint1
     DMF_TRY(bk_scratch(v, pl, b, slot));
     // everything but phase F: the staging stream (pipelined) or the volume's stream
     const hipStream_t sa = staged ? v->stage : v->stream;
-    const PoseX* tab_a = staged ? nullptr : tab + s0;
     unsigned long long* st_a = st;
     if (staged) {
       v->st_slot ^= 1;
       DMF_HIP(hipEventRecord(v->st_in, v->in_stream));
       DMF_HIP(hipStreamWaitEvent(sa, v->st_in, 0));
       if (v->st_free_set[slot]) DMF_HIP(hipStreamWaitEvent(sa, v->st_free[slot], 0));
-      void* t;
-      DMF_TRY(scratch(v, slot ? kScStPoses1 : kScStPoses0, sizeof(PoseX) * (size_t)pl.PS, &t));
-      DMF_TRY(pose_table_into(d_poses + (size_t)s0 * 12, (int)ps, (PoseX*)t, sa));
-      tab_a = (const PoseX*)t;
+    }
+    Src src;  // (a staged depth call's pose table is built here, on the staging stream)
+    DMF_TRY(feed.source(v, s0, ps, pl.PS, staged, slot, sa, src));
+    if (staged) {
       if (st) {
         void* sbuf;
         DMF_TRY(scratch(v, slot ? kScStStats1 : kScStStats0, sizeof(unsigned long long) * kStatSlots * kStatWidth, &sbuf));
@@ -2402,21 +2529,20 @@ static int fuse_bricks(dmf_volume* v, const CamP& cp, const Geom& g, const uint1
     // phase F (launched at once, it would run beside pass B instead, and phase F alone); the
     // pose table and the zeroing above may run beside pass B
     if (staged && v->st_b_set[slot ^ 1]) DMF_HIP(hipStreamWaitEvent(sa, v->st_b_ev[slot ^ 1], 0));
-    BkRaysArgs ra{g, cp, d_depth + (size_t)s0 * cp.H * cp.W, tab_a, prm->dmin_mm, prm->dmax_mm, pl.pkx, (int)pl.ppose,
-                  pl.wg_pose, pl.span, bg, b.rays, b.paths, b.pose_cnt, b.wgb, b.wgl, pl.wgl_stride, b.pose_pairs,
-                  st_a, b.ovl, 0};
+    BkRaysArgs<Src> ra{g, src, (int)pl.ppose, pl.wg_pose, pl.span, bg, b.rays, b.paths, b.pose_cnt, b.wgb, b.wgl,
+                       pl.wgl_stride, b.pose_pairs, st_a, b.ovl, 0};
     if (pl.hash_log > 0) {
       // hashed histogram (8 KB: beside phase F's box), then the overflowed workgroups (if any)
       // with the direct table
       ra.hash_log = pl.hash_log;
       DMF_HIP(hipMemsetAsync(b.ovl, 0, sizeof(uint32_t), sa));
-      hipLaunchKernelGGL(k_bk_rays_hash, dim3(nwg), dim3(kBkPassThreads), sizeof(uint32_t) << pl.hash_log, sa, ra);
+      hipLaunchKernelGGL(k_bk_rays_hash<Src>, dim3(nwg), dim3(kBkPassThreads), sizeof(uint32_t) << pl.hash_log, sa, ra);
       DMF_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_bk_rays_recover, dim3(nf), dim3(kBkPassThreadsBig), sizeof(uint32_t) * ((bg.nbricks + 1) / 2),
-                         sa, ra);
+      hipLaunchKernelGGL(k_bk_rays_recover<Src>, dim3(nf), dim3(kBkPassThreadsBig),
+                         sizeof(uint32_t) * ((bg.nbricks + 1) / 2), sa, ra);
     } else {
-      hipLaunchKernelGGL(k_bk_rays<true>, dim3(nwg), dim3(pl.ab_threads), sizeof(uint32_t) * ((bg.nbricks + 1) / 2), sa,
-                         ra);
+      hipLaunchKernelGGL((k_bk_rays<true, Src>), dim3(nwg), dim3(pl.ab_threads),
+                         sizeof(uint32_t) * ((bg.nbricks + 1) / 2), sa, ra);
     }
     DMF_LAUNCH_CHECK();
     if (staged) {
@@ -2557,8 +2683,53 @@ static int check_fuse(const dmf_volume* v, const dmf_camera* cam, int P, const d
   return DMF_OK;
 }
 
+// dmf_fuse_points*: the plain arguments first (no access to the volume: they are rejected
+// without a device), then what check_fuse checks of the volume.  A scan of N points is S = 1
+// frame of ceil(N / 64) packets; N is bounded so that its packets and rays index in 32 bits
+// (the brick pipeline's own, tighter bound is bk_plan's).
+static int check_fuse_points(const dmf_volume* v, int S, int64_t N, const dmf_fuse_params* prm) {
+  if (!v) return fail(DMF_ERR_INVALID, "null volume");
+  if (!prm) return fail(DMF_ERR_INVALID, "null params");
+  if (N < 1) return fail(DMF_ERR_INVALID, "point count %lld per scan must be >= 1", (long long)N);
+  if (S <= 0 || S > 65535) return fail(DMF_ERR_INVALID, "scan count %d out of range [1,65535]", S);
+  DMF_TRY(require_constructed(v));
+  if (v->xdim > 2048 || v->ydim > 2048 || v->zdim > 2048)
+    return fail(DMF_ERR_RANGE, "fusion grid is limited to 2048 cells per axis (fixed-point DDA)");
+  if (tiled_cells(v->geom().n) > (size_t)UINT32_MAX)
+    return fail(DMF_ERR_RANGE, "fusion grid is limited to 2^32 tiled counter cells");
+  if (N > (int64_t)INT32_MAX - 63) return fail(DMF_ERR_RANGE, "one frame exceeds the 32-bit pair offsets");
+  return DMF_OK;
+}
+
 static const char* variant_kernel(int fv) {
   return fv == DMF_FUSE_LDS_BOX ? kNameLds : (fv == DMF_FUSE_CELL_WALK ? kNameCell : kNameSlab);
+}
+
+// The scratch of fusion calls of up to P frames of `ppose` packets each (dmf_fuse_reserve,
+// dmf_fuse_points_reserve).  Synchronises the stream.
+static int reserve_fusion(dmf_volume* v, int64_t ppose, int P) {
+  const Geom g = v->geom();
+  unsigned long long* st;
+  DMF_TRY(stats_begin(v, &st));
+  if (use_bricks(v, g)) {
+    BkPlan pl;
+    DMF_TRY(bk_plan(v, ppose, g, P, pl));
+    DMF_TRY(bk_attributes());
+    DMF_TRY(fault_words(v));
+    BkBufs set;
+    DMF_TRY(bk_scratch(v, pl, set, 0));
+    if (v->pipelined) {  // the second staging slot, the staging stream, slot pose tables and statistics
+      DMF_TRY(bk_scratch(v, pl, set, 1));
+      DMF_TRY(stage_init(v));
+      void* t;
+      for (int k = 0; k < 2; ++k) {
+        DMF_TRY(scratch(v, k ? kScStPoses1 : kScStPoses0, sizeof(PoseX) * (size_t)pl.PS, &t));
+        DMF_TRY(scratch(v, k ? kScStStats1 : kScStStats0, sizeof(unsigned long long) * kStatSlots * kStatWidth, &t));
+      }
+    }
+  }
+  DMF_HIP(hipStreamSynchronize(v->stream));
+  return DMF_OK;
 }
 
 }  // namespace dmf
@@ -2618,30 +2789,20 @@ int dmf_fuse_reserve(dmf_volume* v, const dmf_camera* cam, int32_t P, uint64_t m
     v->bk_budget = max_scratch_bytes;
   }
   const CamP cp = cam_params(cam);
-  const Geom g = v->geom();
   void* tab;
   DMF_TRY(scratch(v, kScPoses, sizeof(PoseX) * (size_t)P, &tab));
-  unsigned long long* st;
-  DMF_TRY(stats_begin(v, &st));
-  if (use_bricks(v, g)) {
-    BkPlan pl;
-    DMF_TRY(bk_plan(v, cp, g, P, pl));
-    DMF_TRY(bk_attributes());
-    DMF_TRY(fault_words(v));
-    BkBufs set;
-    DMF_TRY(bk_scratch(v, pl, set, 0));
-    if (v->pipelined) {  // the second staging slot, the staging stream, slot pose tables and statistics
-      DMF_TRY(bk_scratch(v, pl, set, 1));
-      DMF_TRY(stage_init(v));
-      void* t;
-      for (int k = 0; k < 2; ++k) {
-        DMF_TRY(scratch(v, k ? kScStPoses1 : kScStPoses0, sizeof(PoseX) * (size_t)pl.PS, &t));
-        DMF_TRY(scratch(v, k ? kScStStats1 : kScStStats0, sizeof(unsigned long long) * kStatSlots * kStatWidth, &t));
-      }
-    }
+  return reserve_fusion(v, cam_packets(cp), P);
+  DMF_API_END
+}
+
+int dmf_fuse_points_reserve(dmf_volume* v, int32_t S, int64_t N, uint64_t max_scratch_bytes) {
+  DMF_API_BEGIN
+  DMF_TRY(check_fuse_points(v, S, N, &kDefaultParamsForCheck));
+  if (max_scratch_bytes && max_scratch_bytes != v->bk_budget) {
+    DMF_TRY(bk_release(v));  // the slots are re-planned against the new budget
+    v->bk_budget = max_scratch_bytes;
   }
-  DMF_HIP(hipStreamSynchronize(v->stream));
-  return DMF_OK;
+  return reserve_fusion(v, scan_packets(N), S);
   DMF_API_END
 }
 
@@ -2655,7 +2816,7 @@ int dmf_fuse_plan(const dmf_volume* v, const dmf_camera* cam, int32_t P, dmf_fus
   out->poses_per_batch = P;
   if (use_bricks(v, g)) {
     BkPlan pl;
-    DMF_TRY(bk_plan(v, cam_params(cam), g, P, pl));
+    DMF_TRY(bk_plan(v, cam_packets(cam_params(cam)), g, P, pl));
     out->brick = 1;
     out->poses_per_batch = (int32_t)pl.PBg;
     out->max_batches = (int32_t)pl.max_batches(P);
@@ -2752,16 +2913,47 @@ static int fuse_device(dmf_volume* v, const dmf_camera* cam, const uint16_t* d_d
   if (d_stats) DMF_TRY(stats_begin(v, &st));
   if (brick) {
     v->last_kernel = variant_kernel(v->fuse_variant);
-    DMF_TRY(fuse_bricks(v, cp, g, d_depth, tab, d_poses, P, prm, d_hits, d_misses, st, d_stats, staged, capturing));
+    const DepthFeed feed{cp, d_depth, tab, d_poses, prm->dmin_mm, prm->dmax_mm};
+    DMF_TRY(fuse_bricks(v, feed, g, P, d_hits, d_misses, st, d_stats, staged, capturing));
   } else {
     const int pkx = (cp.W + 7) / 8;
     if (v->f_event && !capturing) DMF_HIP(hipEventRecord(v->f_event, v->stream));
-    hipLaunchKernelGGL((k_fuse_l<12, 1280>), dim3((unsigned)(pkx * ((cp.H + 7) / 8)), (unsigned)P), dim3(64), 0,
-                       v->stream, g, cp, d_depth, tab, prm->dmin_mm, prm->dmax_mm, pkx, d_hits, d_misses, st);
+    const DepthSrc src{cp, d_depth, tab, prm->dmin_mm, prm->dmax_mm, pkx};
+    hipLaunchKernelGGL((k_fuse_l<12, 1280, DepthSrc>), dim3((unsigned)cam_packets(cp), (unsigned)P), dim3(64), 0,
+                       v->stream, g, src, d_hits, d_misses, st);
     DMF_LAUNCH_CHECK();
     v->last_kernel = kNameLds;
   }
   // (brick pipeline: the layout faults not yet reported go to d_stats[3])
+  if (d_stats) DMF_TRY(stats_end(v, st, d_stats, kStatWidth, brick ? v->d_fault : nullptr));
+  DMF_LAUNCH_CHECK();
+  return DMF_OK;
+}
+
+// dmf_fuse_points_device: fuse_device with the point source (no pose table: pass A and k_fuse_l
+// read the origins as they are); the caller has run check_fuse_points.
+static int fuse_points_dev(dmf_volume* v, const float* d_xyz, const float* d_origins, int32_t S, int64_t N,
+                           int32_t* d_hits, int32_t* d_misses, uint64_t* d_stats, bool allow_stage) {
+  const Geom g = v->geom();
+  const bool brick = use_bricks(v, g);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  DMF_HIP(hipStreamIsCapturing(v->stream, &cs));
+  const bool capturing = cs != hipStreamCaptureStatusNone;
+  const bool staged = brick && allow_stage && v->pipelined && !capturing;
+  unsigned long long* st = nullptr;
+  if (d_stats) DMF_TRY(stats_begin(v, &st));
+  if (brick) {
+    v->last_kernel = variant_kernel(v->fuse_variant);
+    const PointFeed feed{d_xyz, d_origins, N};
+    DMF_TRY(fuse_bricks(v, feed, g, S, d_hits, d_misses, st, d_stats, staged, capturing));
+  } else {
+    if (v->f_event && !capturing) DMF_HIP(hipEventRecord(v->f_event, v->stream));
+    const PointSrc src{d_xyz, d_origins, N};
+    hipLaunchKernelGGL((k_fuse_l<12, 1280, PointSrc>), dim3((unsigned)scan_packets(N), (unsigned)S), dim3(64), 0,
+                       v->stream, g, src, d_hits, d_misses, st);
+    DMF_LAUNCH_CHECK();
+    v->last_kernel = kNameLds;
+  }
   if (d_stats) DMF_TRY(stats_end(v, st, d_stats, kStatWidth, brick ? v->d_fault : nullptr));
   DMF_LAUNCH_CHECK();
   return DMF_OK;
@@ -2785,6 +2977,59 @@ static int take_faults(dmf_volume* v, uint64_t* faults) {
                   "counters of the calls since the last check are invalid)", f)
            : DMF_OK;
 }
+
+struct HostCounters {
+  int32_t *dh, *dm;  // tiled device counters
+  uint64_t* ds;      // 8 statistics counters
+  int32_t* lin;      // one linear counter array (staging)
+};
+// The host forms' counters: the caller's linear x-major hits / misses uploaded into zeroed tiled
+// device counters (the call accumulates onto them), zeroed statistics ...
+static int host_counters_up(dmf_volume* v, const int32_t* hits, const int32_t* misses, HostCounters& hc) {
+  const Geom g = v->geom();
+  const size_t nt = tiled_cells(g.n);
+  const int64_t n = (int64_t)v->ncell;
+  void *dh, *dm, *ds, *lin;
+  DMF_TRY(scratch(v, kScOut0, sizeof(int32_t) * nt, &dh));
+  DMF_TRY(scratch(v, kScOut1, sizeof(int32_t) * nt, &dm));
+  DMF_TRY(scratch(v, kScOut2, sizeof(uint64_t) * 8, &ds));
+  DMF_TRY(scratch(v, kScOut3, sizeof(int32_t) * v->ncell, &lin));
+  DMF_HIP(hipMemsetAsync(dh, 0, sizeof(int32_t) * nt, v->stream));
+  DMF_HIP(hipMemsetAsync(dm, 0, sizeof(int32_t) * nt, v->stream));
+  const dim3 lg((unsigned)((n + 255) / 256));
+  // accumulate onto the caller's linear counters
+  DMF_HIP(hipMemcpyAsync(lin, hits, sizeof(int32_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
+  hipLaunchKernelGGL(k_counter_layout<false>, lg, dim3(256), 0, v->stream, g, (const int32_t*)lin, (int32_t*)dh, n);
+  DMF_LAUNCH_CHECK();
+  DMF_HIP(hipMemcpyAsync(lin, misses, sizeof(int32_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
+  hipLaunchKernelGGL(k_counter_layout<false>, lg, dim3(256), 0, v->stream, g, (const int32_t*)lin, (int32_t*)dm, n);
+  DMF_LAUNCH_CHECK();
+  DMF_HIP(hipMemsetAsync(ds, 0, sizeof(uint64_t) * 8, v->stream));
+  hc = HostCounters{(int32_t*)dh, (int32_t*)dm, (uint64_t*)ds, (int32_t*)lin};
+  return DMF_OK;
+}
+
+// ... and back after the call: linear counters, the layout check, stats[3] += {updates, rays, hits}
+static int host_counters_down(dmf_volume* v, const HostCounters& hc, int32_t* hits, int32_t* misses, int64_t* stats) {
+  const Geom g = v->geom();
+  const int64_t n = (int64_t)v->ncell;
+  const dim3 lg((unsigned)((n + 255) / 256));
+  void *const dh = hc.dh, *const dm = hc.dm, *const ds = hc.ds, *const lin = hc.lin;
+  uint64_t st[4];
+  hipLaunchKernelGGL(k_counter_layout<true>, lg, dim3(256), 0, v->stream, g, (const int32_t*)dh, (int32_t*)lin, n);
+  DMF_LAUNCH_CHECK();
+  DMF_HIP(hipMemcpyAsync(hits, lin, sizeof(int32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
+  DMF_HIP(hipStreamSynchronize(v->stream));
+  hipLaunchKernelGGL(k_counter_layout<true>, lg, dim3(256), 0, v->stream, g, (const int32_t*)dm, (int32_t*)lin, n);
+  DMF_LAUNCH_CHECK();
+  DMF_HIP(hipMemcpyAsync(misses, lin, sizeof(int32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
+  DMF_HIP(hipMemcpyAsync(st, ds, sizeof(st), hipMemcpyDeviceToHost, v->stream));
+  DMF_HIP(hipStreamSynchronize(v->stream));
+  DMF_TRY(take_faults(v, nullptr));
+  if (stats)
+    for (int k = 0; k < 3; ++k) stats[k] += (int64_t)st[k];
+  return DMF_OK;
+}
 }  // namespace dmf
 
 extern "C" {
@@ -2803,45 +3048,42 @@ int dmf_fuse_depth(dmf_volume* v, const dmf_camera* cam, const uint16_t* depth, 
   DMF_TRY(check_fuse(v, cam, P, prm));
   if (!depth || !poses || !hits || !misses) return fail(DMF_ERR_INVALID, "null buffer");
   const size_t HW = (size_t)cam->height * cam->width;
-  const Geom g = v->geom();
-  const size_t nt = tiled_cells(g.n);
-  const int64_t n = (int64_t)v->ncell;
-  void *dd, *dp, *dh, *dm, *ds, *lin;
+  void *dd, *dp;
   DMF_TRY(scratch(v, kScHost1, sizeof(uint16_t) * HW * P, &dd));
   DMF_TRY(scratch(v, kScHost2, sizeof(float) * 12 * P, &dp));
-  DMF_TRY(scratch(v, kScOut0, sizeof(int32_t) * nt, &dh));
-  DMF_TRY(scratch(v, kScOut1, sizeof(int32_t) * nt, &dm));
-  DMF_TRY(scratch(v, kScOut2, sizeof(uint64_t) * 8, &ds));
-  DMF_TRY(scratch(v, kScOut3, sizeof(int32_t) * v->ncell, &lin));
   DMF_HIP(hipMemcpyAsync(dd, depth, sizeof(uint16_t) * HW * P, hipMemcpyHostToDevice, v->stream));
   DMF_HIP(hipMemcpyAsync(dp, poses, sizeof(float) * 12 * P, hipMemcpyHostToDevice, v->stream));
-  DMF_HIP(hipMemsetAsync(dh, 0, sizeof(int32_t) * nt, v->stream));
-  DMF_HIP(hipMemsetAsync(dm, 0, sizeof(int32_t) * nt, v->stream));
-  const dim3 lg((unsigned)((n + 255) / 256));
-  // accumulate onto the caller's linear counters
-  DMF_HIP(hipMemcpyAsync(lin, hits, sizeof(int32_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
-  hipLaunchKernelGGL(k_counter_layout<false>, lg, dim3(256), 0, v->stream, g, (const int32_t*)lin, (int32_t*)dh, n);
-  DMF_LAUNCH_CHECK();
-  DMF_HIP(hipMemcpyAsync(lin, misses, sizeof(int32_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
-  hipLaunchKernelGGL(k_counter_layout<false>, lg, dim3(256), 0, v->stream, g, (const int32_t*)lin, (int32_t*)dm, n);
-  DMF_LAUNCH_CHECK();
-  DMF_HIP(hipMemsetAsync(ds, 0, sizeof(uint64_t) * 8, v->stream));
-  DMF_TRY(fuse_device(v, cam, (const uint16_t*)dd, (const float*)dp, P, prm, (int32_t*)dh, (int32_t*)dm,
-                      (uint64_t*)ds, false));
-  uint64_t st[4];
-  hipLaunchKernelGGL(k_counter_layout<true>, lg, dim3(256), 0, v->stream, g, (const int32_t*)dh, (int32_t*)lin, n);
-  DMF_LAUNCH_CHECK();
-  DMF_HIP(hipMemcpyAsync(hits, lin, sizeof(int32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
-  DMF_HIP(hipStreamSynchronize(v->stream));
-  hipLaunchKernelGGL(k_counter_layout<true>, lg, dim3(256), 0, v->stream, g, (const int32_t*)dm, (int32_t*)lin, n);
-  DMF_LAUNCH_CHECK();
-  DMF_HIP(hipMemcpyAsync(misses, lin, sizeof(int32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
-  DMF_HIP(hipMemcpyAsync(st, ds, sizeof(st), hipMemcpyDeviceToHost, v->stream));
-  DMF_HIP(hipStreamSynchronize(v->stream));
-  DMF_TRY(take_faults(v, nullptr));
-  if (stats)
-    for (int k = 0; k < 3; ++k) stats[k] += (int64_t)st[k];
-  return DMF_OK;
+  HostCounters hc;
+  DMF_TRY(host_counters_up(v, hits, misses, hc));
+  DMF_TRY(fuse_device(v, cam, (const uint16_t*)dd, (const float*)dp, P, prm, hc.dh, hc.dm, hc.ds, false));
+  return host_counters_down(v, hc, hits, misses, stats);
+  DMF_API_END
+}
+
+int dmf_fuse_points_device(dmf_volume* v, const float* d_xyz, const float* d_origins, int32_t S, int64_t N,
+                           const dmf_fuse_params* prm, int32_t* d_hits, int32_t* d_misses, uint64_t* d_stats) {
+  DMF_API_BEGIN
+  if (!d_xyz || !d_origins || !d_hits || !d_misses) return fail(DMF_ERR_INVALID, "null device buffer");
+  DMF_TRY(check_fuse_points(v, S, N, prm));
+  return fuse_points_dev(v, d_xyz, d_origins, S, N, d_hits, d_misses, d_stats, true);
+  DMF_API_END
+}
+
+int dmf_fuse_points(dmf_volume* v, const float* xyz, const float* origins, int32_t S, int64_t N,
+                    const dmf_fuse_params* prm, int32_t* hits, int32_t* misses, int64_t* stats) {
+  DMF_API_BEGIN
+  if (!xyz || !origins || !hits || !misses) return fail(DMF_ERR_INVALID, "null buffer");
+  DMF_TRY(check_fuse_points(v, S, N, prm));
+  const size_t nx = sizeof(float) * 3 * (size_t)S * (size_t)N;
+  void *dx, *dor;
+  DMF_TRY(scratch(v, kScHost1, nx, &dx));
+  DMF_TRY(scratch(v, kScHost2, sizeof(float) * 3 * (size_t)S, &dor));
+  DMF_HIP(hipMemcpyAsync(dx, xyz, nx, hipMemcpyHostToDevice, v->stream));
+  DMF_HIP(hipMemcpyAsync(dor, origins, sizeof(float) * 3 * (size_t)S, hipMemcpyHostToDevice, v->stream));
+  HostCounters hc;
+  DMF_TRY(host_counters_up(v, hits, misses, hc));
+  DMF_TRY(fuse_points_dev(v, (const float*)dx, (const float*)dor, S, N, hc.dh, hc.dm, hc.ds, false));
+  return host_counters_down(v, hc, hits, misses, stats);
   DMF_API_END
 }
 

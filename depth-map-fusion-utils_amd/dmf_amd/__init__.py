@@ -489,6 +489,35 @@ class RayTracingEngine:
                                        C.addressof(params), ptr(hits), ptr(misses), ptr(stats)))
         return hits, misses, stats
 
+    # the same fusion of point clouds with sensor origins
+    def fuse_points(self, volume, xyz, origins, params=None, hits=None, misses=None):
+        """insertPointCloud(scan, origin): xyz (S, N, 3) or (N, 3) float32 world-frame endpoints,
+        origins (S, 3) or (3,) world-frame sensor positions -> what fuse_depth returns.  Point i of
+        scan s is the ray origins[s] -> xyz[s, i], traced exactly as fuse_depth traces a pixel's.  A
+        point with a non-finite coordinate is no ray (pad unequal scans with NaN); there is no range
+        gate (params.dmin_mm / dmax_mm are not applied: filter by range, or mark rejected points NaN)."""
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        origins = np.ascontiguousarray(origins, np.float32)
+        if xyz.ndim == 2:
+            xyz = xyz[None]
+        if origins.ndim == 1:
+            origins = origins[None]
+        if xyz.ndim != 3 or xyz.shape[2] != 3 or origins.shape != (xyz.shape[0], 3):
+            raise ValueError(f"xyz must be (S, N, 3) or (N, 3) and origins (S, 3) or (3,), got {xyz.shape} and "
+                             f"{origins.shape}")
+        n = int(np.prod(volume.dims))
+        for name, a in (("hits", hits), ("misses", misses)):
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.size == n
+                                      and a.flags.c_contiguous):
+                raise ValueError(f"{name} must be a contiguous int32 array of {n} cells (accumulated in place)")
+        hits = np.zeros(n, np.int32) if hits is None else hits
+        misses = np.zeros(n, np.int32) if misses is None else misses
+        stats = np.zeros(3, np.int64)
+        params = params or _lib.default_fuse_params()
+        check(volume._L.dmf_fuse_points(volume._h, ptr(xyz), ptr(origins), xyz.shape[0], xyz.shape[1],
+                                        C.addressof(params), ptr(hits), ptr(misses), ptr(stats)))
+        return hits, misses, stats
+
     def fuse_finalize(self, volume, hits, misses, params=None):
         params = params or _lib.default_fuse_params()
         out = np.zeros(hits.size, np.int16)

@@ -124,6 +124,9 @@ SIGNATURES = {
     "dmf_greedy_set_cover_masks_device": (C.c_int, [_vp, _p, _i32, _i64, _i32, _p, _p]),
     "dmf_fuse_depth": (C.c_int, [_vp, _p, _p, _p, _i32, _p, _p, _p, _p]),
     "dmf_fuse_depth_device": (C.c_int, [_vp, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    "dmf_fuse_points": (C.c_int, [_vp, _p, _p, _i32, _i64, _p, _p, _p, _p]),
+    "dmf_fuse_points_device": (C.c_int, [_vp, _p, _p, _i32, _i64, _p, _p, _p, _p]),
+    "dmf_fuse_points_reserve": (C.c_int, [_vp, _i32, _i64, C.c_uint64]),
     "dmf_fuse_finalize": (C.c_int, [_vp, _p, _p, _p, _p]),
     "dmf_fuse_finalize_device": (C.c_int, [_vp, _p, _p, _p, _p]),
     "dmf_raycast_logodds": (C.c_int, [_vp, _p, _p, _p, _i32, _i32, _i32, _p, _p]),

@@ -251,6 +251,38 @@ int dmf_fuse_depth_device(dmf_volume* v, const dmf_camera* cam, const uint16_t* 
  * a call whose pairs exceed the share runs in more pose batches (dmf_fuse_batches_used),
  * with identical results. */
 int dmf_fuse_reserve(dmf_volume* v, const dmf_camera* cam, int32_t P, uint64_t max_scratch_bytes);
+/* Point-cloud fusion: the insertPointCloud(scan, origin) of the same exact
+ * log-odds fusion.  S scans of N points each: xyz[S][N][3] packed float32 world-frame ray
+ * endpoints, origins[S][3] float32 world-frame sensor positions.  Point i of scan s is the ray
+ * origins[s] -> xyz[s][i], from there on exactly the ray of dmf_fuse_depth (endpoint
+ * acceptance, clip, 1/256-cell quantisation, integer DDA with ties x < y < z; a miss on every
+ * cell before the end cell, a hit on the end cell or a miss there when the endpoint lies
+ * outside the grid), so the points dmf_backproject gives for a frame, fused from the pose's
+ * translation, make the counters of dmf_fuse_depth on that frame bit for bit.
+ *  - A point with a non-finite coordinate is NO ray: no update, not counted in stats[1].  This
+ *    is how organised clouds mark invalid returns, and how scans of unequal length are padded
+ *    to a common N (pad with NaN).  A scan whose origin has a non-finite coordinate traces
+ *    nothing.
+ *  - There is NO range gate: dmin_mm / dmax_mm are not applied (a point has no depth value).
+ *    The caller filters by range, or marks rejected points NaN.  l_hit .. l_max are used only
+ *    by the finalize calls, as for depth frames.
+ *  - The order of the points never changes a counter; it decides which 64 rays share a wave
+ *    (ray index = s * ceil(N/64) * 64 + i), so spatially coherent order is faster.
+ * Host form: linear x-major counters ACCUMULATED, runs the layout check itself, stats[3] +=
+ * {cell updates, rays, hits}.  Device form: tiled counters, only enqueues, d_stats[8] as
+ * dmf_fuse_depth_device.  Both honour the volume's fusion variant, knobs, phase event and input
+ * stream as the depth calls do, and may be mixed with them on one volume without synchronising.
+ * Status (checked before the volume is touched): null volume / params / buffer, N < 1 or S
+ * outside 1..65535 -> DMF_ERR_INVALID; unconstructed volume -> DMF_ERR_STATE; a grid over 2048
+ * cells per axis -> DMF_ERR_RANGE; one scan over the brick pipeline's 32-bit pair offsets or
+ * over its budget -> DMF_ERR_RANGE (the depth calls' "one frame exceeds ..." messages): split
+ * such a scan into several scans with the same origin. */
+int dmf_fuse_points(dmf_volume* v, const float* xyz, const float* origins, int32_t S, int64_t N,
+                    const dmf_fuse_params* prm, int32_t* hits, int32_t* misses, int64_t* stats);
+int dmf_fuse_points_device(dmf_volume* v, const float* d_xyz, const float* d_origins, int32_t S, int64_t N,
+                           const dmf_fuse_params* prm, int32_t* d_hits, int32_t* d_misses, uint64_t* d_stats);
+/* dmf_fuse_reserve for point calls of up to S scans of N points. */
+int dmf_fuse_points_reserve(dmf_volume* v, int32_t S, int64_t N, uint64_t max_scratch_bytes);
 /* Pipelined fusion (an extension, the reference fuses one frame at a time,
  * tests/Raytracing.cpp:70-76).  Declares that the device inputs (d_depth, d_poses) of later
  * dmf_fuse_depth_device calls on this volume are ordered on `stream` (a hipStream_t the
