@@ -34,11 +34,9 @@
 namespace dmf {
 namespace brick {
 
-#if defined(DMF_EXP_BRICK_LOG)  // experiment builds (tools/build_exp.sh): another brick edge, e.g. 4 = 16^3
-constexpr int kLog = DMF_EXP_BRICK_LOG;
-#else
-constexpr int kLog = 5;                 // bricks of 32^3 cells
-#endif
+// bricks of 32^3 cells (16^3 bricks, several 256-lane workgroups of phase F per CU, measured
+// slower: DESIGN.md §5.4; phase F's flush and workgroup size are written for 32)
+constexpr int kLog = 5;
 constexpr int kB = 1 << kLog;
 constexpr int kCells = kB * kB * kB;    // 32768 LDS counters (128 KiB)
 constexpr int kMaxBricks = 32768;       // per-WG LDS histograms of pass A/B (grids <= 1024^3)
@@ -91,7 +89,7 @@ __host__ __device__ inline void decode_ray(uint64_t A, uint64_t B, QRay& r) {
   qray_from(qs, qe, (A >> 63) != 0, r);
 }
 
-// Fine-walk E of the pair (a, b) at the ray start (dmf_fuse.hip dda_setup).
+// Fine-walk E of the pair (a, b) at the ray start (dmf_dda.hpp dda_setup).
 __host__ __device__ inline int32_t e0_pair(const QRay& r, int a, int b) {
   if (r.st[a] && r.st[b]) return (int32_t)((int64_t)r.h0[a] * r.adq[b] - (int64_t)r.h0[b] * r.adq[a]);
   return r.st[a] ? -kNever : (r.st[b] ? kNever : 0);
@@ -154,8 +152,8 @@ __host__ __device__ inline int32_t opaque(int32_t x) {
 
 // a * b for |a|, |b| < 2^23: the low 32 bits of the product, as the plain 32-bit product gives
 // them.  On the device one v_mul_i32_i24 / v_mad_i32_i24, where the compiler's 32-bit integer
-// multiply is a v_mul_lo_u32 / v_mad_u64_u32 (passes A / B: step -0.2 %; the
-// experiment build -DDMF_EXP_MUL32 restores the 32-bit multiply).  The brick path's
+// multiply is a v_mul_lo_u32 / v_mad_u64_u32 (passes A / B: step -0.2 %).  The
+// brick path's
 // operands are in range: brick coordinates and counts <= 1024, |dq| < 2^18 (<= 1024 cells per
 // axis, dmf_fuse.hip brick_path_ok).
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -165,7 +163,7 @@ __host__ __device__ inline int32_t opaque(int32_t x) {
 extern "C" __device__ int32_t dmf_llvm_mul_i24(int32_t, int32_t) __asm("llvm.amdgcn.mul.i24");
 #endif
 __host__ __device__ inline int32_t mul24(int32_t a, int32_t b) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(DMF_EXP_MUL32)
+#if defined(__HIP_DEVICE_COMPILE__)
   return dmf_llvm_mul_i24(a, b);
 #else
   return (int32_t)((uint32_t)a * (uint32_t)b);

@@ -1,0 +1,237 @@
+// dmf_dda.hpp — the exact integer 3D-DDA of a probe ray and the tiled counter
+// layout, shared by the fusion kernels (dmf_fuse.hip) and the log-odds ray-cast
+// (dmf_raycast.hip): clip and quantise camera centre -> endpoint, the int32 walk state, one
+// selection step, and the per-pixel ray of a depth frame.
+#pragma once
+#include "dmf_internal.hpp"
+
+namespace dmf {
+
+constexpr int64_t kQ = 256;  // fixed-point sub-cell resolution (1/256 cell)
+
+__device__ inline int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ inline int32_t clamp32(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// (int64_t) floor(x) as the oracle's x86 conversion gives it (cvttsd2si: NaN and |x| >= 2^63
+// -> INT64_MIN), saturated to +-2^30: a v_cvt_i32_f64 and a select instead of the int64
+// conversion sequence.  Every use clamps the result into [0, n * kQ) with n * kQ <= 2^19
+// (fusion grids <= 2048 cells per axis, check_fuse), so the clamped values are identical.
+__device__ inline int32_t floor_sat32(double x) {
+  const double f = floor(x);
+  return fabs(f) < 9223372036854775808.0 ? (int32_t)fmin(fmax(f, -1073741824.0), 1073741824.0) : -(1 << 30);
+}
+
+__device__ inline void atomic_add_dev(int32_t* p, int32_t v) {
+  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Tiled counter layout: 2x2x4-cell tiles (x, y, z), 16 int32 = one 64-B line, tiles
+// x-major over the padded grid; inside a tile ((x&1)*2 + (y&1))*4 + (z&3).
+struct Tiles {
+  uint32_t ny, nz;  // tiles along y and z
+};
+__host__ __device__ inline Tiles tiles_of(const int n[3]) {
+  return Tiles{(uint32_t)(n[1] + 1) >> 1, (uint32_t)(n[2] + 3) >> 2};
+}
+__host__ __device__ inline uint32_t tile_base(const Tiles& t, int tx, int ty, int tz) {
+  return (((uint32_t)tx * t.ny + (uint32_t)ty) * t.nz + (uint32_t)tz) << 4;
+}
+__host__ __device__ inline uint32_t tiled_index(const Tiles& t, int x, int y, int z) {
+  return tile_base(t, x >> 1, y >> 1, z >> 2) | (uint32_t)(((x & 1) << 3) | ((y & 1) << 2) | (z & 3));
+}
+inline size_t tiled_cells(const int n[3]) {
+  return (size_t)((n[0] + 1) >> 1) * (size_t)((n[1] + 1) >> 1) * (size_t)((n[2] + 3) >> 2) * 16;
+}
+
+// Per-ray DDA state after setup (exact integer walk).
+//
+// The oracle compares next-crossing times T_a = h_a * prod_{b != a} |dq_b| in 64 bits.
+// For a pair of moving axes, sign(T_a - T_b) = sign(E_ab) with
+// E_ab = h_a |dq_b| - h_b |dq_a| (T_a - T_b divided by the third axis' |dq|), and
+// because both next crossings lie within one cell interval of the current time,
+// |E_ab| < (2Q + 1) max|dq| <= 2^29 for grids up to 2048 cells per axis: the walk
+// runs on three int32 differences.  A step along axis a adds 2Q|dq_b| to E_ab (and
+// subtracts 2Q|dq_a| from E_ba).  A pair with a non-moving axis holds a constant that
+// never lets that axis win.
+struct Ray {
+  int c[3];        // current cell
+  int st[3];       // step direction per axis (-1, 0, +1)
+  int32_t E01, E02, E12;  // crossing-time differences (see above)
+  int32_t K[3];    // 2Q |dq_a|
+  int left;        // remaining cell updates (misses + final), 0 = inactive
+  bool end_inside;
+};
+constexpr int32_t kNever = 1 << 30;  // |E| of a pair with a non-moving axis
+
+// One DDA selection (earliest crossing; ties x before y before z): s2 = z, s1 = y, else x.
+__device__ inline void dda_select(int32_t& E01, int32_t& E02, int32_t& E12, int32_t K0, int32_t K1, int32_t K2,
+                                  bool& s0, bool& s1, bool& s2) {
+  const bool b10 = E01 > 0;             // T1 < T0
+  s2 = (b10 ? E12 : E02) > 0;            // T2 < min(T0, T1)
+  s1 = !s2 && b10;
+  s0 = !s2 && !b10;
+  E01 += s0 ? K1 : (s1 ? -K0 : 0);
+  E02 += s0 ? K2 : (s2 ? -K0 : 0);
+  E12 += s1 ? K2 : (s2 ? -K1 : 0);
+}
+
+// (x - min) / delta in double (oracle.cpp dda_ray); a power-of-two delta divides exactly
+// as a multiplication by its (exact) reciprocal, as in bin_axis
+__device__ inline double grid_coord(const Geom& g, int a, float x) {
+  const double t = (double)x - g.mn[a];
+  return g.pow2 ? t * g.inv[a] : t / g.dl[a];
+}
+
+// Grid coordinates of the ray origin.
+__device__ inline void grid_origin(const Geom& g, const float O[3], double go[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) go[a] = grid_coord(g, a, O[a]);
+}
+
+// Clip O->E to the grid and quantise the clipped endpoints to 1/256 cell (clamped
+// into their cells).  Mirrors oracle.cpp dda_ray() lines 752-780 operation for
+// operation; go = grid_origin(O) (one per pose: callers hoist it).  Returns false when
+// the ray misses the grid.
+// A ray that ends inside the grid has t1 overwritten by 1, so of each axis' two slab
+// quotients only the entry one, min(ta, tb), matters, and only when it can exceed t0 >= 0:
+// (0 - go) / D for D > 0, which is <= 0 unless go < 0, and (n - go) / D for D < 0, which is
+// <= 0 unless go > n (division is monotone and keeps the sign) -- so the other divisions
+// are skipped with identical t0 and t1.
+__device__ inline bool dda_quantize_go(const Geom& g, const double go[3], const float E[3], bool end_inside,
+                                       int64_t qs[3], int64_t qe[3]) {
+  double ge[3], D[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ge[a] = grid_coord(g, a, E[a]);
+    D[a] = ge[a] - go[a];
+  }
+  double t0 = 0.0, t1 = 1.0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (D[a] == 0.0) {
+      if (go[a] < 0.0 || go[a] >= (double)g.n[a]) return false;
+    } else if (end_inside) {
+      if (D[a] > 0.0 ? go[a] < 0.0 : go[a] > (double)g.n[a]) {
+        const double lo = (D[a] > 0.0 ? 0.0 - go[a] : (double)g.n[a] - go[a]) / D[a];
+        if (lo > t0) t0 = lo;
+      }
+    } else {
+      double ta = (0.0 - go[a]) / D[a];
+      double tb = ((double)g.n[a] - go[a]) / D[a];
+      if (ta > tb) { const double tt = ta; ta = tb; tb = tt; }
+      if (ta > t0) t0 = ta;
+      if (tb < t1) t1 = tb;
+    }
+  }
+  if (end_inside) { t1 = 1.0; if (t0 > 1.0) t0 = 1.0; }
+  if (t0 > t1) return false;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double gs = go[a] + t0 * D[a];
+    const double gx = end_inside ? ge[a] : go[a] + t1 * D[a];
+    const int32_t n = (int32_t)g.n[a], Q = (int32_t)kQ;
+    const int32_t cs = clamp32(floor_sat32(gs), 0, n - 1);
+    const int32_t ce = end_inside ? floor_sat32(ge[a]) : clamp32(floor_sat32(gx), 0, n - 1);
+    qs[a] = clamp32(floor_sat32(gs * (double)kQ), cs * Q, cs * Q + Q - 1);
+    qe[a] = clamp32(floor_sat32(gx * (double)kQ), ce * Q, ce * Q + Q - 1);
+  }
+  return true;
+}
+
+__device__ inline bool dda_quantize(const Geom& g, const float O[3], const float E[3], bool end_inside, int64_t qs[3],
+                                    int64_t qe[3]) {
+  double go[3];
+  grid_origin(g, O, go);
+  return dda_quantize_go(g, go, E, end_inside, qs, qe);
+}
+
+// Clip/quantise, then set up the walk state (oracle.cpp dda_ray lines 781-806).
+__device__ inline bool dda_setup(const Geom& g, const float O[3], const float E[3], bool end_inside, Ray& R) {
+  int64_t qs[3], qe[3];
+  if (!dda_quantize(g, O, E, end_inside, qs, qe)) return false;
+  int64_t cs[3], ce[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    cs[a] = qs[a] / kQ;  // qs, qe >= 0 and clamped into their cells
+    ce[a] = qe[a] / kQ;
+  }
+  int64_t adq[3], h[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int64_t dq = qe[a] - qs[a];
+    adq[a] = dq < 0 ? -dq : dq;
+    R.st[a] = ce[a] > cs[a] ? 1 : (ce[a] < cs[a] ? -1 : 0);
+    // next crossing numerator in half fixed-point units (oracle.cpp dda_ray)
+    h[a] = R.st[a] > 0 ? 2 * ((cs[a] + 1) * kQ - qs[a]) : 2 * (qs[a] - cs[a] * kQ) + 1;
+    R.K[a] = (int32_t)(2 * kQ * adq[a]);
+  }
+  auto pair = [&](int a, int b) -> int32_t {
+    if (R.st[a] && R.st[b]) return (int32_t)(h[a] * adq[b] - h[b] * adq[a]);
+    return R.st[a] ? -kNever : (R.st[b] ? kNever : 0);
+  };
+  R.E01 = pair(0, 1);
+  R.E02 = pair(0, 2);
+  R.E12 = pair(1, 2);
+  const int nsteps = (int)((ce[0] > cs[0] ? ce[0] - cs[0] : cs[0] - ce[0]) + (ce[1] > cs[1] ? ce[1] - cs[1] : cs[1] - ce[1]) +
+                           (ce[2] > cs[2] ? ce[2] - cs[2] : cs[2] - ce[2]));
+  R.c[0] = (int)cs[0];
+  R.c[1] = (int)cs[1];
+  R.c[2] = (int)cs[2];
+  R.left = nsteps + 1;
+  R.end_inside = end_inside;
+  return true;
+}
+
+// The acceptance of integratePointCloud(cloud, normals) (Volume.hpp:199-228):
+// validPoints(E) && validCoords(getVoxel(E)).  validPoints as float compares (vlo / vhi,
+// dmf_geom.hpp; a NaN endpoint, from a non-finite pose, is outside: the reference's getVoxel
+// gives INT_MIN for it, which validCoords rejects), then getVoxel in double.
+__device__ inline bool endpoint_inside(const Geom& g, const float E[3]) {
+  const bool in = (E[0] >= g.vlo[0]) & (E[0] <= g.vhi[0]) & (E[1] >= g.vlo[1]) & (E[1] <= g.vhi[1]) &
+                  (E[2] >= g.vlo[2]) & (E[2] <= g.vhi[2]);
+  if (!in) return false;
+  return valid_coords(g, bin_axis(g, 0, E[0]), bin_axis(g, 1, E[1]), bin_axis(g, 2, E[2]));
+}
+
+// Per-pixel ray: back-projection (Camera.hpp:24-45) + binning of the endpoint
+// (Volume.hpp:150-156, 199-228) + DDA setup.  Returns the update count (0 = no ray).
+__device__ inline int pixel_ray(const Geom& g, const CamP& cam, const uint16_t* __restrict__ depth,
+                                const PoseX* __restrict__ poses, int p, int r, int c, int dmin, int dmax, Ray& R,
+                                bool& valid) {
+  R.left = 0;
+  valid = false;
+  if (r >= cam.H || c >= cam.W) return 0;
+  const int d = depth[((int64_t)p * cam.H + r) * cam.W + c];
+  if (!(d >= dmin && d < dmax)) return 0;
+  valid = true;
+  const PoseX& T = poses[p];
+  float pc[3], E[3];
+  project(cam, r, c, d, pc);
+  xform(T.f, pc[0], pc[1], pc[2], E);
+  const bool inside = endpoint_inside(g, E);
+  const float O[3] = {T.f[3], T.f[7], T.f[11]};
+  if (!dda_setup(g, O, E, inside, R)) { R.left = 0; return 0; }
+  return R.left;
+}
+
+// The brick path's ray record: pixel_ray up to the quantised endpoints, with the pose's grid
+// origin already computed (go = grid_origin of poses[p]'s translation; d < 0: outside the frame).
+__device__ inline bool pixel_quant_go(const Geom& g, const CamP& cam, int d, const float Tf[12], const double go[3],
+                                      int r, int c, int dmin, int dmax, int64_t qs[3], int64_t qe[3], bool& inside,
+                                      bool& valid) {
+  valid = false;
+  inside = false;
+  if (d < 0 || !(d >= dmin && d < dmax)) return false;
+  valid = true;
+  float pc[3], E[3];
+  project(cam, r, c, d, pc);
+  xform(Tf, pc[0], pc[1], pc[2], E);
+  inside = endpoint_inside(g, E);
+  return dda_quantize_go(g, go, E, inside, qs, qe);
+}
+
+__device__ inline int pixel_depth(const CamP& cam, const uint16_t* __restrict__ depth, int p, int r, int c) {
+  return (r >= cam.H || c >= cam.W) ? -1 : (int)depth[((int64_t)p * cam.H + r) * cam.W + c];
+}
+
+}  // namespace dmf

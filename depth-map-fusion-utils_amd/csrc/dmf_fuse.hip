@@ -21,237 +21,12 @@
 #include <type_traits>
 
 #include "dmf_brick.hpp"
+#include "dmf_dda.hpp"
 #include "dmf_host.hpp"
 
 namespace dmf {
 
-constexpr int64_t kQ = 256;  // fixed-point sub-cell resolution (1/256 cell)
-
-__device__ inline int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ inline int32_t clamp32(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// (int64_t) floor(x) as the oracle's x86 conversion gives it (cvttsd2si: NaN and |x| >= 2^63
-// -> INT64_MIN), saturated to +-2^30: a v_cvt_i32_f64 and a select instead of the int64
-// conversion sequence.  Every use clamps the result into [0, n * kQ) with n * kQ <= 2^19
-// (fusion grids <= 2048 cells per axis, check_fuse), so the clamped values are identical.
-__device__ inline int32_t floor_sat32(double x) {
-  const double f = floor(x);
-  return fabs(f) < 9223372036854775808.0 ? (int32_t)fmin(fmax(f, -1073741824.0), 1073741824.0) : -(1 << 30);
-}
-
-__device__ inline void atomic_add_dev(int32_t* p, int32_t v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Tiled counter layout: 2x2x4-cell tiles (x, y, z), 16 int32 = one 64-B line, tiles
-// x-major over the padded grid; inside a tile ((x&1)*2 + (y&1))*4 + (z&3).
-struct Tiles {
-  uint32_t ny, nz;  // tiles along y and z
-};
-__host__ __device__ inline Tiles tiles_of(const int n[3]) {
-  return Tiles{(uint32_t)(n[1] + 1) >> 1, (uint32_t)(n[2] + 3) >> 2};
-}
-__host__ __device__ inline uint32_t tile_base(const Tiles& t, int tx, int ty, int tz) {
-  return (((uint32_t)tx * t.ny + (uint32_t)ty) * t.nz + (uint32_t)tz) << 4;
-}
-__host__ __device__ inline uint32_t tiled_index(const Tiles& t, int x, int y, int z) {
-  return tile_base(t, x >> 1, y >> 1, z >> 2) | (uint32_t)(((x & 1) << 3) | ((y & 1) << 2) | (z & 3));
-}
-inline size_t tiled_cells(const int n[3]) {
-  return (size_t)((n[0] + 1) >> 1) * (size_t)((n[1] + 1) >> 1) * (size_t)((n[2] + 3) >> 2) * 16;
-}
-
-// Per-ray DDA state after setup (exact integer walk).
-//
-// The oracle compares next-crossing times T_a = h_a * prod_{b != a} |dq_b| in 64 bits.
-// For a pair of moving axes, sign(T_a - T_b) = sign(E_ab) with
-// E_ab = h_a |dq_b| - h_b |dq_a| (T_a - T_b divided by the third axis' |dq|), and
-// because both next crossings lie within one cell interval of the current time,
-// |E_ab| < (2Q + 1) max|dq| <= 2^29 for grids up to 2048 cells per axis: the walk
-// runs on three int32 differences.  A step along axis a adds 2Q|dq_b| to E_ab (and
-// subtracts 2Q|dq_a| from E_ba).  A pair with a non-moving axis holds a constant that
-// never lets that axis win.
-struct Ray {
-  int c[3];        // current cell
-  int st[3];       // step direction per axis (-1, 0, +1)
-  int32_t E01, E02, E12;  // crossing-time differences (see above)
-  int32_t K[3];    // 2Q |dq_a|
-  int left;        // remaining cell updates (misses + final), 0 = inactive
-  bool end_inside;
-};
-constexpr int32_t kNever = 1 << 30;  // |E| of a pair with a non-moving axis
-
-// One DDA selection (earliest crossing; ties x before y before z): s2 = z, s1 = y, else x.
-__device__ inline void dda_select(int32_t& E01, int32_t& E02, int32_t& E12, int32_t K0, int32_t K1, int32_t K2,
-                                  bool& s0, bool& s1, bool& s2) {
-  const bool b10 = E01 > 0;             // T1 < T0
-  s2 = (b10 ? E12 : E02) > 0;            // T2 < min(T0, T1)
-  s1 = !s2 && b10;
-  s0 = !s2 && !b10;
-  E01 += s0 ? K1 : (s1 ? -K0 : 0);
-  E02 += s0 ? K2 : (s2 ? -K0 : 0);
-  E12 += s1 ? K2 : (s2 ? -K1 : 0);
-}
-
-// (x - min) / delta in double (oracle.cpp dda_ray); a power-of-two delta divides exactly
-// as a multiplication by its (exact) reciprocal, as in bin_axis
-__device__ inline double grid_coord(const Geom& g, int a, float x) {
-  const double t = (double)x - g.mn[a];
-  return g.pow2 ? t * g.inv[a] : t / g.dl[a];
-}
-
-// Grid coordinates of the ray origin.
-__device__ inline void grid_origin(const Geom& g, const float O[3], double go[3]) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) go[a] = grid_coord(g, a, O[a]);
-}
-
-// Clip O->E to the grid and quantise the clipped endpoints to 1/256 cell (clamped
-// into their cells).  Mirrors oracle.cpp dda_ray() lines 752-780 operation for
-// operation; go = grid_origin(O) (one per pose: callers hoist it).  Returns false when
-// the ray misses the grid.
-// A ray that ends inside the grid has t1 overwritten by 1, so of each axis' two slab
-// quotients only the entry one, min(ta, tb), matters, and only when it can exceed t0 >= 0:
-// (0 - go) / D for D > 0, which is <= 0 unless go < 0, and (n - go) / D for D < 0, which is
-// <= 0 unless go > n (division is monotone and keeps the sign) -- so the other divisions
-// are skipped with identical t0 and t1.
-__device__ inline bool dda_quantize_go(const Geom& g, const double go[3], const float E[3], bool end_inside,
-                                       int64_t qs[3], int64_t qe[3]) {
-  double ge[3], D[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    ge[a] = grid_coord(g, a, E[a]);
-    D[a] = ge[a] - go[a];
-  }
-  double t0 = 0.0, t1 = 1.0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (D[a] == 0.0) {
-      if (go[a] < 0.0 || go[a] >= (double)g.n[a]) return false;
-    } else if (end_inside) {
-      if (D[a] > 0.0 ? go[a] < 0.0 : go[a] > (double)g.n[a]) {
-        const double lo = (D[a] > 0.0 ? 0.0 - go[a] : (double)g.n[a] - go[a]) / D[a];
-        if (lo > t0) t0 = lo;
-      }
-    } else {
-      double ta = (0.0 - go[a]) / D[a];
-      double tb = ((double)g.n[a] - go[a]) / D[a];
-      if (ta > tb) { const double tt = ta; ta = tb; tb = tt; }
-      if (ta > t0) t0 = ta;
-      if (tb < t1) t1 = tb;
-    }
-  }
-  if (end_inside) { t1 = 1.0; if (t0 > 1.0) t0 = 1.0; }
-  if (t0 > t1) return false;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double gs = go[a] + t0 * D[a];
-    const double gx = end_inside ? ge[a] : go[a] + t1 * D[a];
-    const int32_t n = (int32_t)g.n[a], Q = (int32_t)kQ;
-    const int32_t cs = clamp32(floor_sat32(gs), 0, n - 1);
-    const int32_t ce = end_inside ? floor_sat32(ge[a]) : clamp32(floor_sat32(gx), 0, n - 1);
-    qs[a] = clamp32(floor_sat32(gs * (double)kQ), cs * Q, cs * Q + Q - 1);
-    qe[a] = clamp32(floor_sat32(gx * (double)kQ), ce * Q, ce * Q + Q - 1);
-  }
-  return true;
-}
-
-__device__ inline bool dda_quantize(const Geom& g, const float O[3], const float E[3], bool end_inside, int64_t qs[3],
-                                    int64_t qe[3]) {
-  double go[3];
-  grid_origin(g, O, go);
-  return dda_quantize_go(g, go, E, end_inside, qs, qe);
-}
-
-// Clip/quantise, then set up the walk state (oracle.cpp dda_ray lines 781-806).
-__device__ inline bool dda_setup(const Geom& g, const float O[3], const float E[3], bool end_inside, Ray& R) {
-  int64_t qs[3], qe[3];
-  if (!dda_quantize(g, O, E, end_inside, qs, qe)) return false;
-  int64_t cs[3], ce[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    cs[a] = qs[a] / kQ;  // qs, qe >= 0 and clamped into their cells
-    ce[a] = qe[a] / kQ;
-  }
-  int64_t adq[3], h[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int64_t dq = qe[a] - qs[a];
-    adq[a] = dq < 0 ? -dq : dq;
-    R.st[a] = ce[a] > cs[a] ? 1 : (ce[a] < cs[a] ? -1 : 0);
-    // next crossing numerator in half fixed-point units (oracle.cpp dda_ray)
-    h[a] = R.st[a] > 0 ? 2 * ((cs[a] + 1) * kQ - qs[a]) : 2 * (qs[a] - cs[a] * kQ) + 1;
-    R.K[a] = (int32_t)(2 * kQ * adq[a]);
-  }
-  auto pair = [&](int a, int b) -> int32_t {
-    if (R.st[a] && R.st[b]) return (int32_t)(h[a] * adq[b] - h[b] * adq[a]);
-    return R.st[a] ? -kNever : (R.st[b] ? kNever : 0);
-  };
-  R.E01 = pair(0, 1);
-  R.E02 = pair(0, 2);
-  R.E12 = pair(1, 2);
-  const int nsteps = (int)((ce[0] > cs[0] ? ce[0] - cs[0] : cs[0] - ce[0]) + (ce[1] > cs[1] ? ce[1] - cs[1] : cs[1] - ce[1]) +
-                           (ce[2] > cs[2] ? ce[2] - cs[2] : cs[2] - ce[2]));
-  R.c[0] = (int)cs[0];
-  R.c[1] = (int)cs[1];
-  R.c[2] = (int)cs[2];
-  R.left = nsteps + 1;
-  R.end_inside = end_inside;
-  return true;
-}
-
-// The acceptance of integratePointCloud(cloud, normals) (Volume.hpp:199-228):
-// validPoints(E) && validCoords(getVoxel(E)).  validPoints as float compares (vlo / vhi,
-// dmf_geom.hpp; a NaN endpoint, from a non-finite pose, is outside: the reference's getVoxel
-// gives INT_MIN for it, which validCoords rejects), then getVoxel in double.
-__device__ inline bool endpoint_inside(const Geom& g, const float E[3]) {
-  const bool in = (E[0] >= g.vlo[0]) & (E[0] <= g.vhi[0]) & (E[1] >= g.vlo[1]) & (E[1] <= g.vhi[1]) &
-                  (E[2] >= g.vlo[2]) & (E[2] <= g.vhi[2]);
-  if (!in) return false;
-  return valid_coords(g, bin_axis(g, 0, E[0]), bin_axis(g, 1, E[1]), bin_axis(g, 2, E[2]));
-}
-
-// Per-pixel ray: back-projection (Camera.hpp:24-45) + binning of the endpoint
-// (Volume.hpp:150-156, 199-228) + DDA setup.  Returns the update count (0 = no ray).
-__device__ inline int pixel_ray(const Geom& g, const CamP& cam, const uint16_t* __restrict__ depth,
-                                const PoseX* __restrict__ poses, int p, int r, int c, int dmin, int dmax, Ray& R,
-                                bool& valid) {
-  R.left = 0;
-  valid = false;
-  if (r >= cam.H || c >= cam.W) return 0;
-  const int d = depth[((int64_t)p * cam.H + r) * cam.W + c];
-  if (!(d >= dmin && d < dmax)) return 0;
-  valid = true;
-  const PoseX& T = poses[p];
-  float pc[3], E[3];
-  project(cam, r, c, d, pc);
-  xform(T.f, pc[0], pc[1], pc[2], E);
-  const bool inside = endpoint_inside(g, E);
-  const float O[3] = {T.f[3], T.f[7], T.f[11]};
-  if (!dda_setup(g, O, E, inside, R)) { R.left = 0; return 0; }
-  return R.left;
-}
-
-// The brick path's ray record: pixel_ray up to the quantised endpoints, with the pose's grid
-// origin already computed (go = grid_origin of poses[p]'s translation; d < 0: outside the frame).
-__device__ inline bool pixel_quant_go(const Geom& g, const CamP& cam, int d, const float Tf[12], const double go[3],
-                                      int r, int c, int dmin, int dmax, int64_t qs[3], int64_t qe[3], bool& inside,
-                                      bool& valid) {
-  valid = false;
-  inside = false;
-  if (d < 0 || !(d >= dmin && d < dmax)) return false;
-  valid = true;
-  float pc[3], E[3];
-  project(cam, r, c, d, pc);
-  xform(Tf, pc[0], pc[1], pc[2], E);
-  inside = endpoint_inside(g, E);
-  return dda_quantize_go(g, go, E, inside, qs, qe);
-}
-
-__device__ inline int pixel_depth(const CamP& cam, const uint16_t* __restrict__ depth, int p, int r, int c) {
-  return (r >= cam.H || c >= cam.W) ? -1 : (int)depth[((int64_t)p * cam.H + r) * cam.W + c];
-}
-
+// (the exact DDA, its walk state and the tiled counter layout: dmf_dda.hpp)
 // ---- ray sources.  The fusion kernels that make rays (k_fuse_l, pass A of the
 // brick pipeline) take their rays from a source type: DepthSrc, the pixels of P depth frames
 // behind a pinhole camera, or PointSrc, S scans of N world-frame endpoints with one sensor
@@ -598,9 +373,8 @@ struct BkGeom {
   int nbricks;
 };
 
-// phase F's workgroup: 1024 lanes over a 32^3 brick (one per CU by LDS); an experiment build
-// with 16^3 bricks (DMF_EXP_BRICK_LOG = 4) runs 256-lane workgroups, several per CU
-constexpr int kBkThreads = bk::kLog == 5 ? 1024 : 256;
+// phase F's workgroup: 1024 lanes over a 32^3 brick (one per CU by LDS)
+constexpr int kBkThreads = 1024;
 // passes A/B: 256-lane workgroups (several per CU) while the LDS brick histogram is small;
 // 1024 lanes when it is large (over 8192 bricks: one workgroup per CU by LDS)
 constexpr int kBkPassThreads = 256, kBkPassThreadsBig = 1024, kBkBigHist = 8192;
@@ -637,28 +411,11 @@ __device__ inline uint64_t bk_coarse(const BkGeom& bg, const bk::QRay& R, F&& f)
 }
 
 // Wave-aggregated LDS histogram add: the lanes of a packet walk near-parallel rays and
-// name the same brick at the same coarse step, so one atomic per distinct brick among
-// the active lanes replaces a same-address atomic per lane (which the LDS serialises).
-// Callable from divergent code: the loop runs over the currently active lanes.
-template <bool H16 = false>
-__device__ inline void hist_add_agg(uint32_t* hist, int b) {
-  uint64_t rem = __builtin_amdgcn_ballot_w64(true);
-  const int l = (int)(threadIdx.x & 63);
-  while (rem) {
-    const int leader = __builtin_ctzll(rem);
-    const int bl = __builtin_amdgcn_readlane(b, leader);
-    const uint64_t same = __builtin_amdgcn_ballot_w64(b == bl) & rem;
-    if (l == leader) {
-      if constexpr (H16) atomicAdd(&hist[bl >> 1], (uint32_t)__builtin_popcountll(same) << ((bl & 1) << 4));
-      else atomicAdd(&hist[bl], (uint32_t)__builtin_popcountll(same));
-    }
-    rem &= ~same;
-  }
-}
-
-// hist_add_agg's common case in one step: the lanes naming the first active lane's brick add
-// with one atomic of that lane, the rest (rare: a packet's near-parallel rays cross the same
-// bricks at the same step) each with their own -- no loop over the distinct bricks.
+// name the same brick at the same coarse step, so one atomic for them replaces a
+// same-address atomic per lane (which the LDS serialises).  Callable from divergent code: it
+// runs over the currently active lanes.  One step: the lanes naming the first active lane's
+// brick add with one atomic of that lane, the rest (rare: a packet's near-parallel rays cross
+// the same bricks at the same step) each with their own -- no loop over the distinct bricks.
 template <bool H16 = false>
 __device__ inline void hist_add_first(uint32_t* hist, int b) {
   const int b0 = __builtin_amdgcn_readfirstlane(b);
@@ -698,20 +455,7 @@ __device__ inline bool hash_add(uint32_t* tab, uint32_t mask, int shift, uint32_
   return false;
 }
 
-// hist_add_agg into the hashed histogram; sets *ovf when an insert finds the table full
-__device__ inline void hash_add_agg(uint32_t* tab, uint32_t mask, int shift, int b, uint32_t* ovf) {
-  uint64_t rem = __builtin_amdgcn_ballot_w64(true);
-  const int l = (int)(threadIdx.x & 63);
-  while (rem) {
-    const int leader = __builtin_ctzll(rem);
-    const int bl = __builtin_amdgcn_readlane(b, leader);
-    const uint64_t same = __builtin_amdgcn_ballot_w64(b == bl) & rem;
-    if (l == leader && !hash_add(tab, mask, shift, (uint32_t)bl, (uint32_t)__builtin_popcountll(same))) *ovf = 1u;
-    rem &= ~same;
-  }
-}
-
-// hash_add_agg in one step, as hist_add_first
+// hist_add_first into the hashed histogram; sets *ovf when an insert finds the table full
 __device__ inline void hash_add_first(uint32_t* tab, uint32_t mask, int shift, int b, uint32_t* ovf) {
   const int b0 = __builtin_amdgcn_readfirstlane(b);
   const uint64_t same = __builtin_amdgcn_ballot_w64(b == b0);
@@ -766,9 +510,6 @@ __device__ inline void bk_rays_wg(const BkRaysArgs<Src>& A_, unsigned wg, uint32
   for (int i = threadIdx.x; i < nwords; i += blockDim.x) hist[i] = HASH ? kHashEmpty : 0u;
   __syncthreads();
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = blockDim.x >> 6;
-#if defined(DMF_EXP_A_PRIO)  // experiment builds: pass A's waves at a raised issue priority
-  __builtin_amdgcn_s_setprio(DMF_EXP_A_PRIO);
-#endif
   const int pw = (int)(wg / (unsigned)A_.wg_pose);
   const int q0 = (int)(wg - (unsigned)pw * (unsigned)A_.wg_pose) * A_.span;
   const int64_t pk0 = (int64_t)pw * A_.packets_pose + q0,
@@ -800,14 +541,10 @@ __device__ inline void bk_rays_wg(const BkRaysArgs<Src>& A_, unsigned wg, uint32
       upd += (unsigned long long)(R.nsteps + 1);
       nhit += inside ? 1 : 0;
       path = bk_coarse(bg, R, [&](int b) {
-#if defined(DMF_EXP_A_AGG_LOOP)  // experiment builds: the loop over every distinct brick
-        if constexpr (HASH) hash_add_agg(hist, hmask, hshift, b, &sh[1]);
-        else hist_add_agg<H16>(hist, b);
-#else
-        // (pass A 0.72 -> 0.67 ms at 512^3: one aggregation step instead of a loop)
+        // (pass A 0.72 -> 0.67 ms at 512^3: one aggregation step instead of a loop over every
+        // distinct brick among the lanes)
         if constexpr (HASH) hash_add_first(hist, hmask, hshift, b, &sh[1]);
         else hist_add_first<H16>(hist, b);
-#endif
       });
     }
     nvalid += valid ? 1 : 0;
@@ -1127,15 +864,11 @@ __global__ __launch_bounds__(1024) void k_bk_scan(int nbricks, const uint32_t* _
 // scan (k_bk_scan) in ONE workgroup: one launch instead of three on the chain between pass A
 // and pass B of a pipelined call (config 2: 512 bricks, 64 poses; the chain's launch gaps
 // and three kernels ~47 us of a 1.7-ms call).
-// (experiment builds DMF_EXP_LAYOUT1_BRICKS = 4096: the headline's 512^3 on this path too; its
+// (up to 4096 bricks, the headline's 512^3 on this path too, measured in DESIGN.md §5.4: its
 // 16 KB of counts beside the scan body's 12 KB no longer fit next to phase F's box, and one
-// workgroup reads the 2 MB of per-pose counts alone: measured in DESIGN.md §5.4)
-#if defined(DMF_EXP_LAYOUT1_BRICKS)
-constexpr int kBkLayout1Bricks = DMF_EXP_LAYOUT1_BRICKS, kBkLayout1Poses = 256;
-static_assert(kBkLayout1Bricks <= 4096, "bk_scan_body<false> holds <= 4 counts per lane");
-#else
+// workgroup reads the 2 MB of per-pose counts alone)
 constexpr int kBkLayout1Bricks = 1024, kBkLayout1Poses = 256;
-#endif
+static_assert(kBkLayout1Bricks <= 4096, "bk_scan_body<false> holds <= 4 counts per lane");
 __global__ __launch_bounds__(1024) void k_bk_layout1(int P, const unsigned long long* __restrict__ pose_pairs,
                                                      unsigned long long cap, int max_poses, uint32_t* __restrict__ bt,
                                                      int nbricks, int j, const uint32_t* __restrict__ pose_cnt,
@@ -1229,11 +962,8 @@ __global__ __launch_bounds__(1024) void k_bk_layout1(int P, const unsigned long 
 // Slots: one LDS atomic per lane, whose return is consumed only by the pair's store at the
 // next brick boundary (its latency hides behind that boundary's count_at; B 1.92 -> 1.88 ms;
 // wave-aggregated and run-aggregated takes measured slower).
-// Pass B's store guard (experiment builds: 0 none, 1 a branch around the stores); the
-// default 2 clamps the slot onto a spare record
-#ifndef DMF_B_GUARD
-#define DMF_B_GUARD 2
-#endif
+// Store guard: a slot past the batch's records is clamped onto a spare record (put(); no guard
+// and a branch around the stores were the alternatives).
 // pass B's slot cursor of a brick pass A did not count for the workgroup: every slot taken
 // from it lies at or past any batch's records (pair capacity < the sentinel, bk_plan)
 constexpr uint32_t kBkSlotSentinel = 0xF0000000u;
@@ -1242,15 +972,10 @@ __device__ inline uint32_t bk_e30(int32_t e) {
   return (uint32_t)(e > lim ? lim : (e < -lim ? -lim : e)) & 0x3fffffffu;
 }
 
-
-// (experiment builds DMF_EXP_B_WAVES = n: the compiler keeps B's registers for n waves per SIMD)
-#if defined(DMF_EXP_B_WAVES)
-#define DMF_B_OCC __attribute__((amdgpu_waves_per_eu(DMF_EXP_B_WAVES)))
-#else
-#define DMF_B_OCC
-#endif
+// (no occupancy attribute: held to 5 or 6 waves per SIMD the compiler spilled 10 / 33 registers
+// and B ran slower)
 template <bool SLAB>
-__global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int packets_pose, int wg_pose, int span, BkGeom bg,
+__global__ __launch_bounds__(kBkPassThreadsBig) void k_bk_pairs(int packets_pose, int wg_pose, int span, BkGeom bg,
                                                          const ulonglong2* __restrict__ rays,
                                                          const uint64_t* __restrict__ paths,
                                                          const uint32_t* __restrict__ off,
@@ -1283,11 +1008,9 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
   {
     const uint32_t* row = wg_list + (size_t)blockIdx.x * (size_t)wgl_stride;
     const uint32_t nl = row[0];
-#if DMF_B_GUARD != 0
     // bricks pass A did not count here: any slot taken from them is out of range (checked)
     for (int i = threadIdx.x; i < bg.nbricks; i += blockDim.x) hist[i] = kBkSlotSentinel;
     __syncthreads();
-#endif
     for (uint32_t k = threadIdx.x; k < nl; k += blockDim.x) {
       const int i = (int)(row[1 + k] & 0xffffu);
       hist[i] = off[i] + pbz[i] + wb[i];
@@ -1295,11 +1018,6 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
   }
   __syncthreads();
   uint32_t over = 0;  // one past the lane's largest slot (the layout check; 0 = no pair)
-#if defined(DMF_EXP_B_NOSLOT)
-  uint32_t dslot = blockIdx.x * blockDim.x + threadIdx.x, dmask = 1u;
-  while (dmask * 2u <= total && dmask < 0x80000000u) dmask *= 2u;
-  dmask -= 1u;
-#endif
 #if defined(DMF_EXP_STATS)
   unsigned long long b_iters = 0, b_lanes = 0;
 #endif
@@ -1372,18 +1090,11 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
       return bk_lds_word(x, y, z);
     };
     auto put = [&](uint32_t slot, uint4 e, uint32_t last, uint32_t steps, bool ends) {
-#if DMF_B_GUARD == 1
-      if (slot >= total) {  // only when A and B disagree (reported by the check below)
-        over = slot + 1u;
-        return;
-      }
-#elif DMF_B_GUARD == 2
       // a slot at or past the batch's records (only when A and B disagree, reported by the
       // check below) goes to the spare record at index `total` (pair_cap + 1 are reserved),
       // which phase F never reads: a v_max and a v_min instead of a branch around the stores
       over = max(over, slot + 1u);
       slot = min(slot, total);
-#endif
       if constexpr (SLAB) {
         uint32_t w[5];
         bk::pack20((int32_t)e.x, (int32_t)e.y, (int32_t)e.z, aM, a1, a2, e.w, last, steps, signs >> 22, (uint32_t)M,
@@ -1424,13 +1135,6 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
     // B 1.41 -> 1.37 ms): per ray three reciprocals, per event two fma
     // quotients instead of 64-bit products and float quotient estimates.  Constant axis in each
     // call: no dynamically indexed (scratch) arrays.
-#if defined(DMF_EXP_B_INT_COUNTS)  // experiment builds: the integer counts_at
-    auto counts = [&](int a, int32_t k, int32_t c[3]) {
-      if (a == 0) bk::counts_at(R, 0, k, c);
-      else if (a == 1) bk::counts_at(R, 1, k, c);
-      else bk::counts_at(R, 2, k, c);
-    };
-#else
     bk::QRayF64 F64;
     bk::qray_f64(R, F64);
     auto counts = [&](int a, int32_t k, int32_t c[3]) {
@@ -1438,7 +1142,6 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
       else if (a == 1) bk::counts_at_f64<1>(R, F64, k, c);
       else bk::counts_at_f64<2>(R, F64, k, c);
     };
-#endif
     // the replay of the brick sequence (bk_coarse's order): the crossing axes pass A recorded
     // (path), past its kPathSteps boundaries the stateless next axis from the P's; the brick
     // index moves by a per-axis step
@@ -1446,13 +1149,7 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
     const int32_t nb12 = bg.nb[1] * bg.nb[2];
     const int32_t D0 = bk::mul24(R.st[0], nb12), D1 = bk::mul24(R.st[1], bg.nb[2]), D2 = R.st[2];
     int b = bk_index(bg, cb0, cb1, cb2);
-#if defined(DMF_EXP_B_NOSLOT)  // diagnostic (wrong layout: the check fails, F skips): no slot atomics,
-    // each lane's stores to distinct records, lanes of a wave adjacent (an ideal store stream)
-#define DMF_B_SLOT(b) ((dslot += gridDim.x * blockDim.x) & dmask)
-#else
-#define DMF_B_SLOT(b) atomicAdd(&hist[b], 1u + extra)
-#endif
-    uint32_t slot = DMF_B_SLOT(b);
+    uint32_t slot = atomicAdd(&hist[b], 1u + extra);
     extra = 0;
     uint32_t pword = (uint32_t)path;  // the path word of the current step (steps 0-15: the low one)
     for (int t = 0; t < total; ++t) {
@@ -1485,10 +1182,9 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
       ci0 = c[0];
       ci1 = c[1];
       ci2 = c[2];
-      slot = DMF_B_SLOT(b);
+      slot = atomicAdd(&hist[b], 1u + extra);
       extra = 0;
     }
-#undef DMF_B_SLOT
     put(slot, cur, endc, count_field(R.n[0], R.n[1], R.n[2]), R.end_inside);
   }
 #if defined(DMF_EXP_STATS)
@@ -1499,36 +1195,22 @@ __global__ __launch_bounds__(kBkPassThreadsBig) DMF_B_OCC void k_bk_pairs(int pa
   }
 #endif
   // layout check: the slots taken in each touched brick must be pass A's count for it
-#if DMF_B_GUARD != 0
   __syncthreads();
   {
     const uint32_t* row = wg_list + (size_t)blockIdx.x * (size_t)wgl_stride;
     const uint32_t nl = row[0];
     uint32_t bad = over > total ? 1u : 0u;  // a slot past the records (or from an uncounted brick)
-#if defined(DMF_EXP_LAYOUT_DEBUG)
-    if (bad) printf("B over: wg %u j %d lane %u over %u total %u\n", blockIdx.x, j, threadIdx.x, over, total);
-#endif
     for (uint32_t k = threadIdx.x; k < nl; k += blockDim.x) {
       const uint32_t e = row[1 + k];
       const int i = (int)(e & 0xffffu);
       bad += hist[i] != off[i] + pbz[i] + wb[i] + (e >> 16) ? 1u : 0u;
-#if defined(DMF_EXP_LAYOUT_DEBUG)
-      if (hist[i] != off[i] + pbz[i] + wb[i] + (e >> 16))
-        printf("B count: wg %u j %d brick %d hist %u off %u pbz %u wb %u cnt %u total %u\n", blockIdx.x, j, i, hist[i],
-               off[i], pbz[i], wb[i], e >> 16, total);
-#endif
     }
-#if defined(DMF_EXP_B_NOSLOT)  // (the diagnostic's layout is wrong: one flag per workgroup, F skips)
-    if (threadIdx.x == 0) atomicOr(&ctl[3], 1ull);
-#else
     if (bad) {
       atomicAdd(&fault[0], bad);
       atomicAdd(&fault[1], bad);
       atomicOr(&ctl[3], 1ull);  // phase F skips this batch: its records are not all in place
     }
-#endif
   }
-#endif
 }
 
 // Pair order inside a part: lane-adjacent picks come from S_ORDER far-apart regions of
@@ -1726,12 +1408,9 @@ __global__ __launch_bounds__(kBkThreads) void k_bk_fuse_s(Geom g, BkGeom bg, con
                                                           const uint2* __restrict__ order, uint32_t part_max,
                                                           unsigned long long* __restrict__ ctl,
                                                           int32_t* __restrict__ hits, int32_t* __restrict__ misses,
-                                                          unsigned long long* __restrict__ stats,
-                                                          const ulonglong2* __restrict__ xrays, uint32_t xnrays,
-                                                          uint32_t xnpairs) {
+                                                          unsigned long long* __restrict__ stats) {
   __shared__ uint32_t box[kBkBoxWords + 4];  // counters (skewed), control words
   uint32_t* sh = box + kBkBoxWords;
-  // (xrays / xnrays / xnpairs: used only by the DMF_EXP_F_REBUILD experiment build below)
   // F's stride table, indexed by a record's T = w4 >> 24 (dmf_brick.hpp pack20: the slab code's
   // s and e, the step signs, the major axis M): (dM, d1, d2) the LDS byte strides of the pair's
   // major and minor axes, and the byte offsets from L of the cells of L's slab the code adopts
@@ -1749,13 +1428,6 @@ __global__ __launch_bounds__(kBkThreads) void k_bk_fuse_s(Geom g, BkGeom bg, con
   // pass B's layout check failed for this batch (dmf_fuse_status reports it): its pair
   // records are not all in place, so none is walked
   if (ctl[3] != 0) return;
-#if defined(DMF_EXP_F_PRIO)  // experiment builds: phase F's waves at a raised issue priority
-  __builtin_amdgcn_s_setprio(DMF_EXP_F_PRIO);
-#endif
-#if defined(DMF_EXP_F_REBUILD)
-  xnpairs = (uint32_t)ctl[0];  // the batch's pairs (the stand-in ray ids spread over them)
-  uint32_t sink = 0;           // the proxy's result
-#endif
   for (int i = tid; i < kBkBoxWords; i += blockDim.x) box[i] = 0;
   const uint32_t nparts = (uint32_t)ctl[1];
   const Tiles tl = tiles_of(g.n);
@@ -1805,9 +1477,6 @@ __global__ __launch_bounds__(kBkThreads) void k_bk_fuse_s(Geom g, BkGeom bg, con
     uint32_t cw = 0;
     bool fok = false;
 
-#if defined(DMF_EXP_F_REBUILD)
-    uint32_t kid = 0;  // the prefetched pair's index in the batch
-#endif
     auto decode = [&]() {
       const uint32_t w[5] = {ca.x, ca.y, ca.z, ca.w, cw};
       bk::Slab20 sd;
@@ -1835,47 +1504,8 @@ __global__ __launch_bounds__(kBkThreads) void k_bk_fuse_s(Geom g, BkGeom bg, con
       // the slab's first cell L - d_1 - d_2 (s == 2)
       if (st3.w != 0u) atomicAdd((uint32_t*)(lds + Lb + (uint32_t)(int32_t)(int16_t)(uint16_t)st3.w), 1u);
       if (st3.w > 0xffffu) atomicAdd((uint32_t*)(lds + Lb + (uint32_t)((int32_t)st3.w >> 16)), 1u);
-#if defined(DMF_EXP_F_REBUILD)
-      {
-        // Cost proxy of a compact pair record (B stores <= 8 B, F rebuilds the
-        // slab state): per adopted pair, pass B's per-pair arithmetic on a ray record -- its
-        // 16-B load (a stand-in ray, monotone in the pair index as B's slot order is), the
-        // decode, the f64 reciprocals, the boundary counts at entry and at exit, the entry
-        // state and the slab code.  The records stay the product's (exact results); the
-        // proxy's values only feed a test that is never true.
-        const uint32_t rid = (uint32_t)(((uint64_t)kid * xnrays) / (xnpairs ? xnpairs : 1u));
-        const ulonglong2 rr = xrays[rid];
-        bk::QRay R;
-        bk::decode_ray(rr.x, rr.y, R);
-        bk::QRayF64 F64;
-        bk::qray_f64(R, F64);
-        const int Mx = bk::major_axis(R), m1x = Mx == 0 ? 1 : 0, m2x = Mx == 2 ? 1 : 2;
-        int32_t c0[3], c1[3];
-        const int32_t ka = (int32_t)(kid & 15u), kb = ka + 1;
-        if (Mx == 0) bk::counts_at_f64<0>(R, F64, min(ka, max(R.n[0] - 1, 0)), c0);
-        else if (Mx == 1) bk::counts_at_f64<1>(R, F64, min(ka, max(R.n[1] - 1, 0)), c0);
-        else bk::counts_at_f64<2>(R, F64, min(ka, max(R.n[2] - 1, 0)), c0);
-        if (m1x == 0) bk::counts_at_f64<0>(R, F64, min(kb, max(R.n[0] - 1, 0)), c1);
-        else bk::counts_at_f64<1>(R, F64, min(kb, max(R.n[1] - 1, 0)), c1);
-        const int32_t aMx = bk::pick3(R.adq[0], R.adq[1], R.adq[2], Mx), a1x = bk::pick3(R.adq[0], R.adq[1], R.adq[2], m1x),
-                      a2x = bk::pick3(R.adq[0], R.adq[1], R.adq[2], m2x);
-        const uint32_t KMx = 512u * (uint32_t)aMx, K1x = 512u * (uint32_t)a1x, K2x = 512u * (uint32_t)a2x;
-        int32_t sb1, sb2, sb12;
-        bk::slab_from_pairwise(Mx, bk::e0_pair(R, 0, 1), bk::e0_pair(R, 0, 2), bk::e0_pair(R, 1, 2), sb1, sb2, sb12);
-        const uint32_t eb1 = (uint32_t)sb1 + ((uint32_t)bk::mul24(bk::pick3(c0[0], c0[1], c0[2], Mx), a1x) -
-                                              (uint32_t)bk::mul24(bk::pick3(c0[0], c0[1], c0[2], m1x), aMx)) * 512u;
-        const uint32_t code = bk::slab_code(Mx, sb1, sb2, sb12, KMx, K1x, K2x, c0, c1);
-        const uint32_t xw = (uint32_t)(R.cs[0] + bk::mul24(R.st[0], c0[0])) & 31u,
-                       yw = (uint32_t)(R.cs[1] + bk::mul24(R.st[1], c0[1])) & 31u,
-                       zw = (uint32_t)(R.cs[2] + bk::mul24(R.st[2], c0[2])) & 31u;
-        sink ^= code ^ eb1 ^ bk_lds_word(xw, yw, zw);
-      }
-#endif
     };
     bool more = true;
-#if defined(DMF_EXP_F_XVALU)
-    uint32_t xv = 0;
-#endif
     // lanes in `need` take the next pair indices (one LDS counter atomic, issued by alloc()
     // before the refill's decode so that its return latency hides behind it) and load their
     // records (fetch())
@@ -1892,9 +1522,6 @@ __global__ __launch_bounds__(kBkThreads) void k_bk_fuse_s(Geom g, BkGeom bg, con
         const uint32_t k = base + (uint32_t)lane_prefix(need);
         fok = k < n;
         const uint32_t ob = bk_order<S_ORDER>(k, n);
-#if defined(DMF_EXP_F_REBUILD)
-        kid = p0 + ob;
-#endif
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_a, ob * 16u, 0, 0);
         ca = make_uint4(v[0], v[1], v[2], v[3]);
         cw = __builtin_amdgcn_raw_buffer_load_b32(rs_w, ob * 4u, 0, 0);
@@ -1937,9 +1564,6 @@ __global__ __launch_bounds__(kBkThreads) void k_bk_fuse_s(Geom g, BkGeom bg, con
               const uint32_t k = base + (uint32_t)lane_prefix(take);
               fok = k < n;
               const uint32_t ob = bk_order<S_ORDER>(k, n);
-#if defined(DMF_EXP_F_REBUILD)
-              kid = p0 + ob;
-#endif
               const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_a, ob * 16u, 0, 0);
               ca = make_uint4(v[0], v[1], v[2], v[3]);
               cw = __builtin_amdgcn_raw_buffer_load_b32(rs_w, ob * 4u, 0, 0);
@@ -1972,16 +1596,7 @@ __global__ __launch_bounds__(kBkThreads) void k_bk_fuse_s(Geom g, BkGeom bg, con
           atomicAdd((uint32_t*)(lds + cur), 1u);
           if (c1 || c2) atomicAdd((uint32_t*)(lds + p1), 1u);
           if (c1 && c2) atomicAdd((uint32_t*)(lds + p2), 1u);
-#if defined(DMF_EXP_F_XLDS)  // diagnostic (wrong counts): every walk atomic twice
-          atomicAdd((uint32_t*)(lds + cur), 1u);
-          if (c1 || c2) atomicAdd((uint32_t*)(lds + p1), 1u);
-          if (c1 && c2) atomicAdd((uint32_t*)(lds + p2), 1u);
-#endif
         }
-#if defined(DMF_EXP_F_XVALU)  // diagnostic: independent VALU per slab, kept by a never-true test
-        xv = ((xv ^ cur) + b1) ^ (b2 << 1);
-        xv = ((xv ^ b12) + p1) ^ (p2 << 2);
-#endif
         cur = p2 + dM;
         b1 += c1 ? K1mM : K1;
         b2 += c2 ? K2mM : K2;
@@ -1990,37 +1605,15 @@ __global__ __launch_bounds__(kBkThreads) void k_bk_fuse_s(Geom g, BkGeom bg, con
       r -= UNROLL;
       DMF_TACC(t_walk, tw0);
     }
-#if defined(DMF_EXP_F_XVALU)
-    if (xv == 0x9e3779b9u + n) atomicAdd(&hits[0], 0);
-#endif
     DMF_T(tf0);
     __syncthreads();
-    if constexpr (bk::kLog != 5) {
-      // (experiment builds with another brick edge: the generic mapping of k_bk_fuse)
-      for (int e = tid; e < bk::kCells; e += blockDim.x) {
-        const int tile = e >> 4, w16 = e & 15;
-        const int tx = tile >> (2 * bk::kLog - 3), ty = (tile >> (bk::kLog - 2)) & ((bk::kB >> 1) - 1),
-                  tz = tile & ((bk::kB >> 2) - 1);
-        const int lx = tx * 2 + (w16 >> 3), ly = ty * 2 + ((w16 >> 2) & 1), lz = tz * 4 + (w16 & 3);
-        const int li = lx * kBkSx + ly * kBkSy + lz;
-        const uint32_t v = box[li];
-        if (v) {
-          box[li] = 0;
-          const uint32_t ti = tiled_index(tl, lo0 + lx, lo1 + ly, lo2 + lz);
-          const int32_t mi = (int32_t)(v & 0xffffu), hv = (int32_t)(v >> 16);
-          if (mi) atomic_add_dev(&misses[ti], mi);
-          if (hv) atomic_add_dev(&hits[ti], hv);
-          ++nflush;
-        }
-      }
-    } else
     // flush (one device atomic per non-zero cell and counter): lane tid takes cells
     // e = tid + 1024 k of the brick in the tiled order (16 lanes per 64-B counter line).  The
     // cell's box word and its counter index inside the brick move by per-k constants, so
     // the index math is done once per part, not per cell (cell e: tile e >> 4 = (tx, ty, tz)
     // with tx = k >> 1, ty = 8 (k & 1) + (t0 >> 3), tz = t0 & 7 for t0 = tid >> 4).
     {
-      static_assert(bk::kLog != 5 || kBkThreads == 1024, "flush strides: 32^3-cell bricks, 1024 lanes");
+      static_assert(bk::kLog == 5 && kBkThreads == 1024, "flush strides: 32^3-cell bricks, 1024 lanes");
       const int t0 = tid >> 4, w16 = tid & 15;
       const int li0 = (w16 >> 3) * kBkSx + (2 * (t0 >> 3) + ((w16 >> 2) & 1)) * kBkSy + 4 * (t0 & 7) + (w16 & 3);
       const uint32_t ti0 = tile_base(tl, lo0 >> 1, lo1 >> 1, lo2 >> 2) +
@@ -2043,9 +1636,6 @@ __global__ __launch_bounds__(kBkThreads) void k_bk_fuse_s(Geom g, BkGeom bg, con
     __syncthreads();
     DMF_TACC(t_flush, tf0);
   }
-#if defined(DMF_EXP_F_REBUILD)
-  if (sink == 0x9e3779b9u + xnrays) atomicAdd(&hits[0], 0);  // never true in practice: keeps the proxy
-#endif
   if (stats) {
     for (int o = 32; o > 0; o >>= 1) nflush += __shfl_down(nflush, o, 64);
     if (l == 0 && nflush) atomicAdd(&stats[6], nflush);
@@ -2162,16 +1752,8 @@ static bool use_bricks(const dmf_volume* v, const Geom& g) {
 // 1 % faster than 4 at 512^3 and at config 2, the others slower); with 8-slab blocks a wave
 // refills at >= 16 idle lanes (sweep 16/20/24/32, picks over 16/32/64 regions: serial -1 %,
 // config 2 -0.5 %, pipelined within the box's drift)
-#if defined(DMF_EXP_F_UNROLL)  // experiment builds: slabs per walk block
-constexpr int kBkUnroll = DMF_EXP_F_UNROLL;
-#else
 constexpr int kBkUnroll = 8;
-#endif
-#if defined(DMF_EXP_F_REFILL)  // experiment builds: refill threshold / pick spread of phase F
-constexpr int kBkRefill = DMF_EXP_F_REFILL, kBkSpread = DMF_EXP_F_SPREAD;
-#else
-constexpr int kBkRefill = 16, kBkSpread = 32;
-#endif
+constexpr int kBkRefill = 16, kBkSpread = 32;  // refill threshold / pick spread of phase F
 constexpr const char* kNameSlab = "dmf::k_bk_fuse_s<16, 32, 8>";
 constexpr const char* kNameCell = "dmf::k_bk_fuse<16, 8, 8>";
 constexpr const char* kNameLds = "dmf::k_fuse_l<12, 1280>";
@@ -2236,9 +1818,6 @@ static int bk_plan(const dmf_volume* v, int64_t ppose, const Geom& g, int P, BkP
   const uint64_t one_pose = (uint64_t)rays_pose * (uint64_t)pl.max_pairs_ray;  // pairs of one pose, at most
   if (one_pose > (uint64_t)UINT32_MAX) return fail(DMF_ERR_RANGE, "one frame exceeds the 32-bit pair offsets");
   pl.ab_threads = pl.bg.nbricks > kBkBigHist ? kBkPassThreadsBig : kBkPassThreads;
-#if defined(DMF_EXP_AB_THREADS)  // experiment builds: passes A/B workgroup size below kBkBigHist bricks
-  if (pl.bg.nbricks <= kBkBigHist) pl.ab_threads = DMF_EXP_AB_THREADS;
-#endif
   // packets per workgroup of passes A/B (>= 16 per wave; the histogram's zero + flush
   // amortised over >= 64 packets per 1k bricks).  Up to 512 bricks (grids <= 256^3) the
   // histogram is small enough for 8 per wave: config 2 fusion 2.05 -> 2.02 ms, while 384^3
@@ -2489,16 +2068,19 @@ static int fuse_bricks(dmf_volume* v, const Feed& feed, const Geom& g, int P, in
   // pass A with 16-bit histogram counts (a workgroup's pairs per brick <= span * 64 rays; the
   // plan holds span <= 1023)
   if ((int64_t)pl.span * 64 > 65535) return fail(DMF_ERR_RANGE, "pass A span %d exceeds 16-bit counts", pl.span);
-  const unsigned nf = (unsigned)cu_count(v->device);
-  // phase F's persistent workgroups: one per CU (32^3 bricks); an experiment build with
-  // smaller bricks holds as many per CU as fit
-  unsigned nfF = nf;
-  if constexpr (bk::kLog != 5) {
-    int per = 0;
-    DMF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per, (const void*)k_bk_fuse_s<kBkRefill, kBkSpread, kBkUnroll>, kBkThreads, 0));
-    nfF = nf * (unsigned)std::max(per, 1);
-  }
+  const unsigned nf = (unsigned)cu_count(v->device);  // phase F's persistent workgroups: one per CU
+  // pass B and the brick scan, each one launch whatever the variant / grid size
+  auto pass_b = [&](auto kernel, unsigned nwg, hipStream_t s, int64_t j) {
+    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(pl.ab_threads), pl.hist_bytes, s, (int)pl.ppose, pl.wg_pose, pl.span, bg,
+                       (const ulonglong2*)b.rays, (const uint64_t*)b.paths, (const uint32_t*)b.off,
+                       (const uint32_t*)b.pose_base, (const uint32_t*)b.wgb, (const uint32_t*)b.bt, (int)j,
+                       (const uint32_t*)b.wgl, pl.wgl_stride, b.pra, b.prb, b.ctl, v->d_fault,
+                       (int)std::min<int64_t>(v->knob[DMF_KNOB_FAULT_INJECT], 1 << 20), st);
+  };
+  auto scan = [&](auto kernel, hipStream_t s, int64_t j) {
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(1024), 0, s, bg.nbricks, (const uint32_t*)b.cnt, b.off, b.part_pref, b.ctl,
+                       b.order, pl.part_max, (const uint32_t*)b.bt, (int)j, pl.split_cu);
+  };
   for (int64_t s0 = 0; s0 < P; s0 += pl.PS) {
     const int64_t ps = std::min<int64_t>(pl.PS, P - s0);
     const unsigned nwg = (unsigned)(ps * pl.wg_pose);
@@ -2585,27 +2167,12 @@ static int fuse_bricks(dmf_volume* v, const Feed& feed, const Geom& g, int P, in
         hipLaunchKernelGGL(k_bk_batch_counts, dim3((unsigned)((bg.nbricks + 255) / 256)), dim3(256), 0, sj,
                            bg.nbricks, (int)j, (const uint32_t*)b.bt, (const uint32_t*)b.pose_cnt, b.pose_base, b.cnt);
         DMF_LAUNCH_CHECK();
+        if (bg.nbricks > 4096) scan(k_bk_scan<true>, sj, j);
+        else scan(k_bk_scan<false>, sj, j);
       }
-      if (layout1) {
-      } else if (bg.nbricks > 4096)
-        hipLaunchKernelGGL(k_bk_scan<true>, dim3(1), dim3(1024), 0, sj, bg.nbricks, (const uint32_t*)b.cnt, b.off,
-                           b.part_pref, b.ctl, b.order, pl.part_max, (const uint32_t*)b.bt, (int)j, pl.split_cu);
-      else
-        hipLaunchKernelGGL(k_bk_scan<false>, dim3(1), dim3(1024), 0, sj, bg.nbricks, (const uint32_t*)b.cnt, b.off,
-                           b.part_pref, b.ctl, b.order, pl.part_max, (const uint32_t*)b.bt, (int)j, pl.split_cu);
       DMF_LAUNCH_CHECK();
-      if (slab)
-        hipLaunchKernelGGL(k_bk_pairs<true>, dim3(nwg), dim3(pl.ab_threads), pl.hist_bytes, sj, (int)pl.ppose,
-                           pl.wg_pose, pl.span, bg, (const ulonglong2*)b.rays, (const uint64_t*)b.paths, (const uint32_t*)b.off,
-                           (const uint32_t*)b.pose_base, (const uint32_t*)b.wgb, (const uint32_t*)b.bt, (int)j,
-                           (const uint32_t*)b.wgl, pl.wgl_stride, b.pra, b.prb, b.ctl,
-                           v->d_fault, (int)std::min<int64_t>(v->knob[DMF_KNOB_FAULT_INJECT], 1 << 20), st);
-      else
-        hipLaunchKernelGGL(k_bk_pairs<false>, dim3(nwg), dim3(pl.ab_threads), pl.hist_bytes, sj, (int)pl.ppose,
-                           pl.wg_pose, pl.span, bg, (const ulonglong2*)b.rays, (const uint64_t*)b.paths, (const uint32_t*)b.off,
-                           (const uint32_t*)b.pose_base, (const uint32_t*)b.wgb, (const uint32_t*)b.bt, (int)j,
-                           (const uint32_t*)b.wgl, pl.wgl_stride, b.pra, b.prb, b.ctl,
-                           v->d_fault, (int)std::min<int64_t>(v->knob[DMF_KNOB_FAULT_INJECT], 1 << 20), st);
+      if (slab) pass_b(k_bk_pairs<true>, nwg, sj, j);
+      else pass_b(k_bk_pairs<false>, nwg, sj, j);
       DMF_LAUNCH_CHECK();
       // the call's phase F begins (not while capturing: the record would become a graph node
       // and the caller's event would never be re-recorded by the graph's launches)
@@ -2620,10 +2187,9 @@ static int fuse_bricks(dmf_volume* v, const Feed& feed, const Geom& g, int P, in
         v->st_b_set[slot] = true;
       }
       if (slab)
-        hipLaunchKernelGGL((k_bk_fuse_s<kBkRefill, kBkSpread, kBkUnroll>), dim3(nfF), dim3(kBkThreads), 0, v->stream, g, bg,
+        hipLaunchKernelGGL((k_bk_fuse_s<kBkRefill, kBkSpread, kBkUnroll>), dim3(nf), dim3(kBkThreads), 0, v->stream, g, bg,
                            (const uint4*)b.pra, (const uint32_t*)b.prb, (const uint32_t*)b.off, (const uint32_t*)b.cnt,
-                           (const uint2*)b.order, pl.part_max, b.ctl, d_hits, d_misses, st, (const ulonglong2*)b.rays,
-                           (uint32_t)(ps * pl.ppose * 64), (uint32_t)std::min<uint64_t>(pl.pair_cap, UINT32_MAX));
+                           (const uint2*)b.order, pl.part_max, b.ctl, d_hits, d_misses, st);
       else
         hipLaunchKernelGGL((k_bk_fuse<16, 8, 8>), dim3(nf), dim3(kBkThreads), 0, v->stream, g, bg, (const uint4*)b.pra,
                            (const uint2*)b.prb, (const uint32_t*)b.off, (const uint32_t*)b.cnt,
@@ -2681,6 +2247,10 @@ static int check_fuse(const dmf_volume* v, const dmf_camera* cam, int P, const d
   if (tiled_cells(v->geom().n) > (size_t)UINT32_MAX)
     return fail(DMF_ERR_RANGE, "fusion grid is limited to 2^32 tiled counter cells");
   return DMF_OK;
+}
+
+int check_fuse_call(const dmf_volume* v, const dmf_camera* cam, int P) {
+  return check_fuse(v, cam, P, &kDefaultParamsForCheck);
 }
 
 // dmf_fuse_points*: the plain arguments first (no access to the volume: they are rejected
@@ -3130,357 +2700,6 @@ int dmf_fuse_finalize(dmf_volume* v, const int32_t* hits, const int32_t* misses,
   DMF_LAUNCH_CHECK();
   DMF_TRY(dmf_fuse_finalize_device(v, (const int32_t*)dh, (const int32_t*)dm, prm, (int16_t*)dout));
   DMF_HIP(hipMemcpyAsync(out, dout, sizeof(int16_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
-  DMF_HIP(hipStreamSynchronize(v->stream));
-  return DMF_OK;
-  DMF_API_END
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------ log-odds ray-cast
-//   What a camera at pose T sees in a fused grid: per pixel the first cell
-// of the fusion's own probe ray (depth range_mm) whose log-odds reach a threshold.  Three kernels:
-//  k_rc_mask   — one streaming pass over the int16 grid: a 1-bit-per-cell mask of L >= threshold
-//                in the occupancy bitmask's 8x8x8-tile layout (occ_bit, dmf_internal.hpp) and one
-//                bit per tile over it (512^3: 16 MiB + 32 KiB, against 256 MiB of int16);
-//  k_rc_bricks — one bit per 32^3-cell brick (4x4x4 tiles) from the tile bits;
-//  k_rc_cast   — one lane per pixel: dda_setup once, then the dda_select walk.  The tile bit is
-//                read when the tile changes, a mask word only inside a non-empty tile and only
-//                when the word changes.  <true> also reads the brick bit when the brick changes and
-//                leaves a wholly empty brick or tile in one exact jump (rc_jump) instead of cell by
-//                cell.  Skipping removes loads and tests of empty cells, never cells of the
-//                sequence: the reported cell is the plain walk's.
-namespace dmf {
-
-struct RcTiles {
-  uint32_t nty, ntz, ntiles;   // 8x8x8-cell tiles along y and z, and in all (x-major, as occ_bit)
-  uint32_t nby, nbz, nbricks;  // 32^3-cell bricks (4x4x4 tiles) likewise
-};
-static RcTiles rc_tiles(const Geom& g) {
-  const uint32_t ntx = ((uint32_t)g.n[0] + 7u) >> 3, nty = ((uint32_t)g.n[1] + 7u) >> 3, ntz = ((uint32_t)g.n[2] + 7u) >> 3;
-  const uint32_t nbx = (ntx + 3u) >> 2, nby = (nty + 3u) >> 2, nbz = (ntz + 3u) >> 2;
-  return RcTiles{nty, ntz, ntx * nty * ntz, nby, nbz, nbx * nby * nbz};
-}
-
-// One workgroup per 32 consecutive tiles = 512 mask words = one word of the tile level.  Thread
-// (tile j = i & 31, word w = i >> 5) reads the word's 4 y-rows of 8 z-cells (16 B each): a wave's
-// loads are 2 x 4 rows of up to 512 contiguous bytes.  The words go through LDS so that the
-// workgroup's 2 KiB of the mask are stored in order.  Cells past the grid (partial tiles) are 0.
-constexpr int kRcMaskThreads = 512;
-constexpr int kRcDefaultWalk = 2;  // DMF_KNOB_RAYCAST_WALK = 0 (measured: DESIGN.md §5.11)
-__global__ __launch_bounds__(kRcMaskThreads) void k_rc_mask(Geom g, RcTiles tl, const int16_t* __restrict__ L,
-                                                            int threshold, uint32_t* __restrict__ fine,
-                                                            uint32_t* __restrict__ coarse) {
-  __shared__ uint32_t sw[kRcMaskThreads];
-  __shared__ uint32_t sany[16];
-  const int i = threadIdx.x, j = i & 31, w = i >> 5;
-  const uint32_t t = blockIdx.x * 32u + (uint32_t)j;
-  uint32_t word = 0;
-  if (t < tl.ntiles) {
-    const uint32_t tz = t % tl.ntz, r = t / tl.ntz;
-    const int x = (int)(r / tl.nty) * 8 + (w >> 1), y0 = (int)(r % tl.nty) * 8 + (w & 1) * 4, z0 = (int)tz * 8;
-    if (x < g.n[0]) {
-#pragma unroll
-      for (int dy = 0; dy < 4; ++dy) {
-        const int y = y0 + dy;
-        if (y < g.n[1]) {
-          const int16_t* row = L + (((int64_t)x * g.n[1] + y) * g.n[2] + z0);
-          uint32_t b = 0;
-          if (z0 + 8 <= g.n[2] && ((uintptr_t)row & 15) == 0) {
-            const uint4 q = *(const uint4*)row;
-            const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              b |= (uint32_t)((int)(int16_t)(u[k] & 0xffffu) >= threshold) << (2 * k);
-              b |= (uint32_t)((int)(int16_t)(u[k] >> 16) >= threshold) << (2 * k + 1);
-            }
-          } else {
-            for (int k = 0; k < 8 && z0 + k < g.n[2]; ++k) b |= (uint32_t)((int)row[k] >= threshold) << k;
-          }
-          word |= b << (8 * dy);
-        }
-      }
-    }
-  }
-  sw[j * 16 + w] = word;
-  // a wave holds words 2k (lanes 0-31) and 2k + 1 (lanes 32-63) of the 32 tiles
-  const uint64_t any = __builtin_amdgcn_ballot_w64(word != 0u);
-  if ((i & 63) == 0) {
-    sany[w] = (uint32_t)any;
-    sany[w + 1] = (uint32_t)(any >> 32);
-  }
-  __syncthreads();
-  const uint32_t o = blockIdx.x * (uint32_t)kRcMaskThreads + (uint32_t)i;
-  if (o < tl.ntiles * 16u) fine[o] = sw[i];
-  if (i == 0) {
-    uint32_t a = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) a |= sany[k];
-    coarse[blockIdx.x] = a;  // bit j = tile 32 * block + j holds a solid cell
-  }
-}
-
-// One lane per brick: the OR of its 4x4x4 tile bits (tiles past the grid's last tile row are
-// absent).  One workgroup per 32 bricks = one word of the brick level.
-__global__ __launch_bounds__(64) void k_rc_bricks(RcTiles tl, uint32_t ntx, const uint32_t* __restrict__ coarse,
-                                                  uint32_t* __restrict__ bricks) {
-  const uint32_t b = blockIdx.x * 32u + (threadIdx.x & 31u);
-  bool any = false;
-  if (threadIdx.x < 32 && b < tl.nbricks) {
-    const uint32_t bz = b % tl.nbz, r = b / tl.nbz, by = r % tl.nby, bx = r / tl.nby;
-    for (uint32_t dx = 0; dx < 4; ++dx)
-      for (uint32_t dy = 0; dy < 4; ++dy) {
-        const uint32_t tx = bx * 4 + dx, ty = by * 4 + dy;
-        if (tx >= ntx || ty >= tl.nty) continue;
-        for (uint32_t tz = bz * 4; tz < bz * 4 + 4 && tz < tl.ntz; ++tz) {
-          const uint32_t t = (tx * tl.nty + ty) * tl.ntz + tz;
-          any |= (coarse[t >> 5] >> (t & 31u)) & 1u;
-        }
-      }
-  }
-  const uint64_t m = __builtin_amdgcn_ballot_w64(any);
-  if (threadIdx.x == 0) bricks[blockIdx.x] = (uint32_t)m;
-}
-
-// floor(x / k) for 0 <= x < 2^35, 1 <= k < 2^29 with quotient < 2^12: a float estimate (within 1 of
-// the quotient: three roundings of 2^-24 relative each) and exact integer correction.
-__device__ inline int32_t rc_div(int64_t x, int32_t k) {
-  int32_t q = (int32_t)((float)x * __builtin_amdgcn_rcpf((float)k));
-  int64_t r = x - (int64_t)q * k;
-  if (r < 0) { --q; r += k; }
-  if (r < 0) { --q; r += k; }
-  if (r >= k) { ++q; r -= k; }
-  if (r >= k) { ++q; }
-  return q;
-}
-
-// Exact jump out of the aligned cube of (m + 1)^3 cells (m = 7 or 31) that holds the current cell:
-// the walk state after the crossing that leaves the cube, and the number of steps that takes.
-// In the cube, axis a can still make r_a crossings; its (r_a + 1)-th leaves.  The earliest of the
-// three leaving events in the walk's own order (crossing time, ties x < y < z) is found as
-// dda_select finds the next crossing, from F_ab = E_ab + r_a K_b - r_b K_a (the crossing-time
-// difference of the two leaving events); every crossing of another axis b that
-// precedes that event (a*, r*) in the same order is taken with it: #{k >= 0 : k K_a* < X} for
-// b > a*, <= X for b < a*, X = (h_a* + 2Q r*) |dq_b| - h_b |dq_a*| = +-E + r* K_b.  A step along a
-// adds K_b to E_ab and takes K_a from E_ba, so n_a steps per axis move E_ab by n_a K_b - n_b K_a.
-// A non-moving axis has K = 0, r = 0 and |E| = kNever against a moving one: it neither leaves
-// nor steps.  Returns the steps; more than the ray has left means the ray ends in the cube.
-__device__ inline int rc_jump(int m, int& c0, int& c1, int& c2, int st0, int st1, int st2, int32_t& E01, int32_t& E02,
-                              int32_t& E12, int32_t K0, int32_t K1, int32_t K2) {
-  const int r0 = st0 > 0 ? m - (c0 & m) : (st0 < 0 ? (c0 & m) : 0);
-  const int r1 = st1 > 0 ? m - (c1 & m) : (st1 < 0 ? (c1 & m) : 0);
-  const int r2 = st2 > 0 ? m - (c2 & m) : (st2 < 0 ? (c2 & m) : 0);
-  const int64_t F01 = (int64_t)E01 + (int64_t)r0 * K1 - (int64_t)r1 * K0;
-  const int64_t F02 = (int64_t)E02 + (int64_t)r0 * K2 - (int64_t)r2 * K0;
-  const int64_t F12 = (int64_t)E12 + (int64_t)r1 * K2 - (int64_t)r2 * K1;
-  const bool b10 = F01 > 0;
-  const bool s2 = (b10 ? F12 : F02) > 0, s1 = !s2 && b10;
-  // crossings of axis b before the leaving event of a*: d = h_a* |dq_b| - h_b |dq_a*|
-  auto before = [](int64_t d, int rs, int32_t kb, int32_t ka, bool b_after) -> int {
-    const int64_t x = d + (int64_t)rs * kb;
-    if (x < 0 || ka == 0) return 0;
-    const int32_t q = rc_div(x, ka);
-    return b_after ? (int)(q + ((int64_t)q * ka < x ? 1 : 0)) : (int)q + 1;
-  };
-  int n0, n1, n2;
-  if (s2) {
-    n2 = r2 + 1;
-    n0 = before(-(int64_t)E02, r2, K0, K2, false);
-    n1 = before(-(int64_t)E12, r2, K1, K2, false);
-  } else if (s1) {
-    n1 = r1 + 1;
-    n0 = before(-(int64_t)E01, r1, K0, K1, false);
-    n2 = before((int64_t)E12, r1, K2, K1, true);
-  } else {
-    n0 = r0 + 1;
-    n1 = before((int64_t)E01, r0, K1, K0, true);
-    n2 = before((int64_t)E02, r0, K2, K0, true);
-  }
-  c0 += st0 * n0;
-  c1 += st1 * n1;
-  c2 += st2 * n2;
-  E01 = (int32_t)((uint32_t)E01 + (uint32_t)n0 * (uint32_t)K1 - (uint32_t)n1 * (uint32_t)K0);
-  E02 = (int32_t)((uint32_t)E02 + (uint32_t)n0 * (uint32_t)K2 - (uint32_t)n2 * (uint32_t)K0);
-  E12 = (int32_t)((uint32_t)E12 + (uint32_t)n1 * (uint32_t)K2 - (uint32_t)n2 * (uint32_t)K1);
-  return n0 + n1 + n2;
-}
-
-// One 64-lane workgroup per 8x8 pixel packet of one pose (neighbouring rays share tiles and
-// words).  Outputs per pixel: depth (rayTraceVolume's value of the surface voxel, k_zbuffer's
-// arithmetic; -1 = none) and cell (getHashId; all ones = none); either may be null.  stats (may
-// be null): {rays with a non-empty sequence, rays with a surface cell}.
-template <bool JUMP>
-__global__ __launch_bounds__(64) void k_rc_cast(Geom g, RcTiles tl, CamP cam, const PoseX* __restrict__ poses,
-                                                int range_mm, int packets_x, const uint32_t* __restrict__ fine,
-                                                const uint32_t* __restrict__ coarse,
-                                                const uint32_t* __restrict__ bricks, int32_t* __restrict__ depth,
-                                                uint64_t* __restrict__ cell, unsigned long long* __restrict__ stats) {
-  stats = stat_slot(stats);
-  const int l = threadIdx.x;
-  const int pr = (blockIdx.x / packets_x) * 8 + (l >> 3), pc = (blockIdx.x % packets_x) * 8 + (l & 7);
-  const bool in_image = pr < cam.H && pc < cam.W;
-  const PoseX& T = poses[blockIdx.y];
-  Ray R;
-  R.left = 0;
-  if (in_image) {
-    float pcam[3], E[3];
-    project(cam, pr, pc, range_mm, pcam);
-    xform(T.f, pcam[0], pcam[1], pcam[2], E);
-    const bool inside = endpoint_inside(g, E);
-    const float O[3] = {T.f[3], T.f[7], T.f[11]};
-    if (!dda_setup(g, O, E, inside, R)) R.left = 0;
-  }
-  int32_t E01 = R.E01, E02 = R.E02, E12 = R.E12;
-  const int32_t K0 = R.K[0], K1 = R.K[1], K2 = R.K[2];
-  const int st0 = R.st[0], st1 = R.st[1], st2 = R.st[2];
-  int c0 = R.c[0], c1 = R.c[1], c2 = R.c[2], left = R.left;
-  const bool entered = left > 0;
-  bool found = false, tile_solid = false, brick_solid = false;
-  uint32_t last_t = 0xffffffffu, last_b = 0xffffffffu, last_w = 0xffffffffu, word = 0;
-  while (left > 0) {
-    const uint32_t t = (((uint32_t)c0 >> 3) * tl.nty + ((uint32_t)c1 >> 3)) * tl.ntz + ((uint32_t)c2 >> 3);
-    if (t != last_t) {
-      last_t = t;
-      if (JUMP) {  // (the cell-by-cell walk has no use for the brick level: it would only add a test)
-        const uint32_t b = (((uint32_t)c0 >> 5) * tl.nby + ((uint32_t)c1 >> 5)) * tl.nbz + ((uint32_t)c2 >> 5);
-        if (b != last_b) {
-          last_b = b;
-          brick_solid = (bricks[b >> 5] >> (b & 31u)) & 1u;
-        }
-      }
-      tile_solid = (!JUMP || brick_solid) && ((coarse[t >> 5] >> (t & 31u)) & 1u);
-      if (JUMP && !tile_solid) {
-        // every cell up to the crossing that leaves the empty cube is empty
-        const int n = rc_jump(brick_solid ? 7 : 31, c0, c1, c2, st0, st1, st2, E01, E02, E12, K0, K1, K2);
-        if (n >= left) break;  // the ray ends inside it
-        left -= n;
-        continue;
-      }
-    }
-    if (tile_solid) {
-      const uint32_t wi = (t << 4) | (((uint32_t)c0 & 7u) << 1) | (((uint32_t)c1 & 7u) >> 2);
-      if (wi != last_w) {
-        last_w = wi;
-        word = fine[wi];
-      }
-      if ((word >> ((((uint32_t)c1 & 3u) << 3) | ((uint32_t)c2 & 7u))) & 1u) {
-        found = true;
-        break;
-      }
-    }
-    if (--left == 0) break;
-    bool s0, s1, s2;
-    dda_select(E01, E02, E12, K0, K1, K2, s0, s1, s2);
-    c0 += s0 ? st0 : 0;
-    c1 += s1 ? st1 : 0;
-    c2 += s2 ? st2 : 0;
-  }
-  if (in_image) {
-    int32_t d = -1;
-    uint64_t h = ~0ull;
-    if (found) {
-      h = hash_id(c0, c1, c2);
-      // the voxel centre from the cell index as reverseRayTraceFast forms it, then k_zbuffer's depth
-      const float x = (float)((double)c0 * g.dl[0] + g.mn[0]), y = (float)((double)c1 * g.dl[1] + g.mn[1]),
-                  z = (float)((double)c2 * g.dl[2] + g.mn[2]);
-      float tc[3];
-      xform(T.i, (float)((double)x + g.hdl[0]), (float)((double)y + g.hdl[1]), (float)((double)z + g.hdl[2]), tc);
-      d = to_int_x86((double)roundf(tc[2] * 1000.0f));
-    }
-    const int64_t o = ((int64_t)blockIdx.y * cam.H + pr) * cam.W + pc;
-    if (depth) depth[o] = d;
-    if (cell) cell[o] = h;
-  }
-  if (stats) {
-    unsigned long long ne = entered ? 1 : 0, nf = found ? 1 : 0;
-    for (int o = 32; o > 0; o >>= 1) {
-      ne += __shfl_down(ne, o, 64);
-      nf += __shfl_down(nf, o, 64);
-    }
-    if (l == 0) {
-      if (ne) atomicAdd(&stats[0], ne);
-      if (nf) atomicAdd(&stats[1], nf);
-    }
-  }
-}
-
-// The plain arguments first (no access to the volume: they are rejected without a device), then
-// what the fusion checks (constructed, camera, P in 1..65535, grid size).
-static int check_raycast(const dmf_volume* v, const dmf_camera* cam, const void* logodds, const void* poses, int32_t P,
-                         int32_t range_mm) {
-  if (!v || !cam || !logodds || !poses) return fail(DMF_ERR_INVALID, "null argument");
-  if (range_mm < 1 || range_mm > 65535) return fail(DMF_ERR_INVALID, "range_mm %d out of range [1,65535]", range_mm);
-  if (P < 0) return fail(DMF_ERR_INVALID, "negative pose count %d", P);
-  return check_fuse(v, cam, P, &kDefaultParamsForCheck);
-}
-
-static int raycast_device(dmf_volume* v, const dmf_camera* cam, const int16_t* d_logodds, const float* d_poses,
-                          int32_t P, int32_t threshold, int32_t range_mm, int32_t* d_depth, uint64_t* d_cell,
-                          uint64_t* d_stats) {
-  const CamP cp = cam_params(cam);
-  const Geom g = v->geom();
-  const RcTiles tl = rc_tiles(g);
-  PoseX* tab = nullptr;
-  DMF_TRY(pose_table(v, d_poses, P, true, &tab));
-  // the tile words, then the brick words, in one buffer
-  const uint32_t ncoarse = (tl.ntiles + 31u) / 32u, nbw = (tl.nbricks + 31u) / 32u;
-  void *fine, *coarse;
-  DMF_TRY(scratch(v, kScRcFine, sizeof(uint32_t) * 16 * (size_t)tl.ntiles, &fine));
-  DMF_TRY(scratch(v, kScRcCoarse, sizeof(uint32_t) * ((size_t)ncoarse + nbw), &coarse));
-  uint32_t* const bricks = (uint32_t*)coarse + ncoarse;
-  unsigned long long* st = nullptr;
-  if (d_stats) DMF_TRY(stats_begin(v, &st));
-  hipLaunchKernelGGL(k_rc_mask, dim3(ncoarse), dim3(kRcMaskThreads), 0, v->stream, g, tl, d_logodds, threshold,
-                     (uint32_t*)fine, (uint32_t*)coarse);
-  DMF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_rc_bricks, dim3(nbw), dim3(64), 0, v->stream, tl, ((uint32_t)g.n[0] + 7u) >> 3,
-                     (const uint32_t*)coarse, bricks);
-  DMF_LAUNCH_CHECK();
-  const int pkx = (cp.W + 7) / 8;
-  const dim3 grid((unsigned)(pkx * ((cp.H + 7) / 8)), (unsigned)P);
-  // DMF_KNOB_RAYCAST_WALK (dmf_diag.h): 1 = cell by cell, 2 = empty bricks and tiles jumped
-  const int64_t kw = v->knob[DMF_KNOB_RAYCAST_WALK];
-  if (((kw == 1 || kw == 2) ? (int)kw : kRcDefaultWalk) == 2) {
-    hipLaunchKernelGGL(k_rc_cast<true>, grid, dim3(64), 0, v->stream, g, tl, cp, tab, range_mm, pkx,
-                       (const uint32_t*)fine, (const uint32_t*)coarse, (const uint32_t*)bricks, d_depth, d_cell, st);
-  } else {
-    hipLaunchKernelGGL(k_rc_cast<false>, grid, dim3(64), 0, v->stream, g, tl, cp, tab, range_mm, pkx,
-                       (const uint32_t*)fine, (const uint32_t*)coarse, (const uint32_t*)bricks, d_depth, d_cell, st);
-  }
-  DMF_LAUNCH_CHECK();
-  if (d_stats) DMF_TRY(stats_end(v, st, d_stats, 2));
-  return DMF_OK;
-}
-
-}  // namespace dmf
-
-extern "C" {
-
-int dmf_raycast_logodds_device(dmf_volume* v, const dmf_camera* cam, const int16_t* d_logodds, const float* d_poses,
-                               int32_t P, int32_t threshold, int32_t range_mm, int32_t* d_depth, uint64_t* d_cell,
-                               uint64_t* d_stats) {
-  DMF_API_BEGIN
-  DMF_TRY(check_raycast(v, cam, d_logodds, d_poses, P, range_mm));
-  return raycast_device(v, cam, d_logodds, d_poses, P, threshold, range_mm, d_depth, d_cell, d_stats);
-  DMF_API_END
-}
-
-int dmf_raycast_logodds(dmf_volume* v, const dmf_camera* cam, const int16_t* logodds, const float* poses, int32_t P,
-                        int32_t threshold, int32_t range_mm, int32_t* depth, uint64_t* cell) {
-  DMF_API_BEGIN
-  DMF_TRY(check_raycast(v, cam, logodds, poses, P, range_mm));
-  const size_t n = (size_t)P * (size_t)cam->height * (size_t)cam->width;
-  void *dl, *dp, *dd = nullptr, *dc = nullptr;
-  DMF_TRY(scratch(v, kScOut2, sizeof(int16_t) * v->ncell, &dl));
-  DMF_TRY(scratch(v, kScHost2, sizeof(float) * 12 * (size_t)P, &dp));
-  if (depth) DMF_TRY(scratch(v, kScOut0, sizeof(int32_t) * n, &dd));
-  if (cell) DMF_TRY(scratch(v, kScOut1, sizeof(uint64_t) * n, &dc));
-  DMF_HIP(hipMemcpyAsync(dl, logodds, sizeof(int16_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
-  DMF_HIP(hipMemcpyAsync(dp, poses, sizeof(float) * 12 * (size_t)P, hipMemcpyHostToDevice, v->stream));
-  DMF_TRY(raycast_device(v, cam, (const int16_t*)dl, (const float*)dp, P, threshold, range_mm, (int32_t*)dd,
-                         (uint64_t*)dc, nullptr));
-  if (depth) DMF_HIP(hipMemcpyAsync(depth, dd, sizeof(int32_t) * n, hipMemcpyDeviceToHost, v->stream));
-  if (cell) DMF_HIP(hipMemcpyAsync(cell, dc, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, v->stream));
   DMF_HIP(hipStreamSynchronize(v->stream));
   return DMF_OK;
   DMF_API_END

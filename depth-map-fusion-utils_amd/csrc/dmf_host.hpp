@@ -62,7 +62,7 @@ enum ScratchSlot {
   kScOgP0, kScOgP1, kScOgFinal, kScOgOcc,  // OccupancyGrid reorganization (dmf_ogrid.hip)
   kScRevItems,  // reverseRayTraceFast's item-ordered (spatial order) result masks (dmf_trace.hip)
   kScBkOvf, kScBkOvf1,  // pass A's hashed-histogram overflow lists, per staging slot (dmf_fuse.hip)
-  kScRcFine, kScRcCoarse,  // the log-odds ray-cast's solid mask and its tile + brick levels (dmf_fuse.hip)
+  kScRcFine, kScRcCoarse,  // the log-odds ray-cast's solid mask and its tile + brick levels (dmf_raycast.hip)
   // surface extraction (dmf_surface.hip): the solid, free and surface masks, the per-row counts
   // and their scan, the {surface, solid} counters, and the host forms' output staging
   kScSfSolid, kScSfFree, kScSfSurf, kScSfCounts, kScSfBases, kScSfTotals, kScSfHash, kScSfXyz, kScSfNrm
@@ -71,8 +71,11 @@ enum ScratchSlot {
 // Striped statistics: kernels add into slot (block % kStatSlots) of a zeroed buffer
 // of kStatSlots x kStatWidth counters (one hot address per counter serialises at the
 // memory side); stats_end() sums the slots into the caller's counters.
+// DMF_EXP_STATS is the one diagnostic build the sources keep: an instrument (extra counters
+// 7..19 and s_memtime phase timers, read by bench.py and tools/exp_*.py; DESIGN.md §5.5-5.8
+// rest on them), not an alternative implementation -- those live in the history.
 #if defined(DMF_EXP_STATS)
-constexpr int kStatSlots = 256, kStatWidth = 20;  // diagnostic builds: extra counters 7..19
+constexpr int kStatSlots = 256, kStatWidth = 20;
 #else
 constexpr int kStatSlots = 256, kStatWidth = 8;
 #endif
@@ -104,6 +107,9 @@ int finalize_tiles(dmf_volume* v, const int32_t* d_hits, const int32_t* d_misses
                    int16_t* d_out, int64_t t0, int64_t t1, hipStream_t stream);
 int tile_rows(const dmf_volume* v, int64_t* ntx, int64_t* tiles_per_row);
 int check_camera(const dmf_camera* c);
+// What every fusion call checks of the volume, the camera and the pose count P (dmf_fuse.hip
+// check_fuse; the ray-cast of dmf_raycast.hip walks the same rays under the same limits).
+int check_fuse_call(const dmf_volume* v, const dmf_camera* cam, int P);
 
 // Lazily (re)build the float-accumulated enumeration list (reverseRayTrace / rayTraceVolume).
 int ensure_enumeration(dmf_volume* v);

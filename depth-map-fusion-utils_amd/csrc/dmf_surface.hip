@@ -3,7 +3,7 @@
 // (L <= free_threshold) face neighbour, in ascending x-major cell index (= ascending getHashId),
 // each with its hash, voxel centre and a normal from the face neighbours' log-odds.  An ordered,
 // exact stream compaction in which almost every cell is rejected:
-//  k_sf_mask    — one streaming pass over the grid (k_rc_mask's load pattern, dmf_fuse.hip): the
+//  k_sf_mask    — one streaming pass over the grid (k_rc_mask's load pattern, dmf_raycast.hip): the
 //                 solid and the free 1-bit-per-cell masks in the occupancy bitmask's 8x8x8-tile
 //                 layout (occ_bit, dmf_internal.hpp), and the number of solid cells;
 //  k_sf_surface — bit level: surface = solid & (free shifted along -x, +x, -y, +y, -z, +z), the

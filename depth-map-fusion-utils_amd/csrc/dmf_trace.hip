@@ -21,46 +21,20 @@
 
 namespace dmf {
 
-// Register budgets of the march kernels: DMF_EXP_REV_WAVES / DMF_EXP_FWD_WAVES = n keeps their
-// registers for n waves per SIMD (experiment builds override them)
-// k_reverse_x at 6 waves per SIMD (round 6: the next sample computed while a sample's loads are
-// in flight needs 4 more VGPRs; at 7 waves 2 spill: 4.49-4.51 ms at 6 waves vs 4.56 at 7 with
-// the spill and 4.54-4.56 without the precompute at 7; round 5: 7 waves, 72
-// VGPRs, 5.19 vs 5.21 ms at 6; 8 waves spilled and lost)
-#if !defined(DMF_EXP_REV_WAVES)
-#define DMF_EXP_REV_WAVES 6
-#endif
-#define DMF_REV_OCC __attribute__((amdgpu_waves_per_eu(DMF_EXP_REV_WAVES)))
-// The queue marches' empty-space jumps: 0 (default) = the target is computed from the cube's
-// faces moved in by Geom::jmarg and needs no check (round 6: 5.19 -> 4.77 ms per 128 poses,
-// samples 937M -> 649M, DESIGN.md §5.5, profiles/r06y); 1 = the landing sample is evaluated and
-// checked against the cube before the jump is taken (experiment builds)
-#ifndef DMF_REV_VERIFY_JUMPS
-#define DMF_REV_VERIFY_JUMPS 0
-#endif
-// The forward marches' jumps: 0 (default) = the line's point at the landing is checked against
-// the cube shrunk by twice the rounding margin, and the entry jump's target is taken as computed
-// (round 6: 6.16 -> 5.51 ms per 128 poses, samples 1.10G -> 0.77G, DESIGN.md §5.6,
-// profiles/r06z); 1 = the landing sample is evaluated and checked (experiment builds)
-#ifndef DMF_FWD_VERIFY_JUMPS
-#define DMF_FWD_VERIFY_JUMPS 0
-#endif
+// Register budget of k_reverse_x: its registers kept for 6 waves per SIMD (round 6: the next
+// sample computed while a sample's loads are in flight needs 4 more VGPRs; at 7 waves 2 spill:
+// 4.49-4.51 ms at 6 waves vs 4.56 at 7 with the spill and 4.54-4.56 without the precompute at 7,
+// DESIGN.md §5.5; round 5: 7 waves, 72 VGPRs, 5.19 vs 5.21 ms at 6; 8 waves spilled and lost).
+// The forward marches carry no occupancy attribute.
+constexpr int kRevWaves = 6;
+// The marches' empty-space jumps evaluate no landing sample: the reverse march's target is
+// computed from the cube's faces moved in by Geom::jmarg (round 6: 5.19 -> 4.77 ms per 128
+// poses, samples 937M -> 649M, DESIGN.md §5.5, profiles/r06y); the forward marches check the
+// line's point at the landing against the cube shrunk by twice the rounding margin and take the
+// entry jump's target as computed (round 6: 6.16 -> 5.51 ms per 128 poses, samples 1.10G ->
+// 0.77G, DESIGN.md §5.6, profiles/r06z).
 // The reverse march computes sample s + 1 while sample s's occupancy and distance loads are in
-// flight (used when the step is a plain step; a jump or the centroid's cell recomputes): 1 (the
-// default, round 6); 0 = one sample computed per step (experiment builds)
-#ifndef DMF_EXP_REV_PRECOMP
-#define DMF_EXP_REV_PRECOMP 1
-#endif
-#if defined(DMF_EXP_FWD_WAVES)
-#define DMF_FWD_OCC __attribute__((amdgpu_waves_per_eu(DMF_EXP_FWD_WAVES)))
-#else
-#define DMF_FWD_OCC
-#endif
-#if defined(DMF_EXP_FWDQ_WAVES)
-#define DMF_FWDQ_OCC __attribute__((amdgpu_waves_per_eu(DMF_EXP_FWDQ_WAVES)))
-#else
-#define DMF_FWDQ_OCC
-#endif
+// flight (used when the step is a plain step; a jump or the centroid's cell recomputes; round 6).
 
 struct EnumList {
   const float* axes;  // xs | ys | zs (float-accumulated, RayTracingEngine.hpp:54-56)
@@ -252,10 +226,8 @@ struct RevLane {
   int32_t slot;
   float tz;             // camera-frame z of the centroid (z-range test)
   uint32_t occi, occw;  // cached occupancy word
-#if DMF_EXP_REV_PRECOMP
   float pn[3];          // sample pns, computed ahead
   int pns;
-#endif
 };
 
 __device__ inline bool valid_points_f(const Geom& g, const float p[3]) {
@@ -292,14 +264,12 @@ constexpr int kRevStatN = 11;
 // (and inside the volume) so does every sample between them — none can hit an
 // occupied cell, the centroid's cell (occupied) or leave the volume.  j is computed from the
 // cube's faces moved in by Geom::jmarg, which puts sample j inside the cube without evaluating
-// it (DMF_REV_VERIFY_JUMPS = 0, the default), or estimated from the faces themselves and
-// verified by evaluating sample j exactly (= 1).
+// it.
 __device__ inline int rev_step(const Geom& g, const DevVol& vd, RevLane& L, int depth0, int max_steps,
                                int64_t& samples, unsigned long long* rst) {
   (void)rst;
   if (L.s >= max_steps) return 3;
   float p[3];
-#if DMF_EXP_REV_PRECOMP
   // sample s was computed by the previous step while that step's loads were in flight
   if (L.pns == L.s) {
     p[0] = L.pn[0];
@@ -308,9 +278,6 @@ __device__ inline int rev_step(const Geom& g, const DevVol& vd, RevLane& L, int 
   } else {
     march_sample(L.cen, L.v, depth0 + L.s, p);
   }
-#else
-  march_sample(L.cen, L.v, depth0 + L.s, p);
-#endif
   ++samples;
   int a, b, c;
   if (!valid_points_f(g, p)) return 2;
@@ -328,14 +295,11 @@ __device__ inline int rev_step(const Geom& g, const DevVol& vd, RevLane& L, int 
   const uint32_t bl = ((uint32_t)ba * (uint32_t)vd.nb[1] + (uint32_t)bb) * (uint32_t)vd.nb[2] + (uint32_t)bc;
   const int dpre = vd.bdist[bl];
   if ((ob >> 5) != L.occi) { L.occi = ob >> 5; L.occw = vd.occ[L.occi]; }
-#if DMF_EXP_REV_PRECOMP
   march_sample(L.cen, L.v, depth0 + L.s + 1, L.pn);  // the next sample, while the loads are in flight
   L.pns = L.s + 1;
-#endif
   if ((L.occw >> (ob & 31)) & 1u) return 1;
   if (bl != L.known_full) {
     const int d = dpre;
-#if !DMF_REV_VERIFY_JUMPS
     if (d > 0) {
       // the jump target from the cube's exit faces moved toward the sample by g.jmarg: no
       // sample of the jump is evaluated here; the target j is the next one marched, and the
@@ -364,42 +328,6 @@ __device__ inline int rev_step(const Geom& g, const DevVol& vd, RevLane& L, int 
     } else {
       DMF_RS(12, 1);
     }
-#else
-    if (d > 0) {
-      const int R = d - 1;  // bricks within R of this one are empty
-      const int bx[3] = {ba, bb, bc};
-      int clo[3], chi[3];   // cell range of the empty cube, [clo, chi)
-      float fdmax = 3.0e38f;
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) {
-        clo[ax] = max(bx[ax] - R, 0) << vd.bsh;
-        chi[ax] = min((bx[ax] + R + 1) << vd.bsh, g.n[ax]);
-        if (L.v[ax] == 0.0f) continue;
-        const float face = (float)(g.mn[ax] + (double)(L.v[ax] > 0.0f ? chi[ax] : clo[ax]) * g.dl[ax]);
-        fdmax = fminf(fdmax, (face - L.cen[ax]) * L.rv[ax]);
-      }
-      const float jf = floorf(fdmax) - (float)depth0 - 2.0f;
-      if (jf > (float)(L.s + 1) && jf < (float)max_steps) {
-        const int j = (int)jf;
-        DMF_RS(4, 1);
-        float q[3];
-        march_sample(L.cen, L.v, depth0 + j, q);
-        ++samples;
-        if (valid_points_f(g, q)) {
-          int qa, qb, qc;
-          bin_point(g, q, qa, qb, qc);
-          if (qa >= clo[0] && qa < chi[0] && qb >= clo[1] && qb < chi[1] && qc >= clo[2] && qc < chi[2]) {
-            DMF_RS(5, 1);
-            DMF_RS(6, j - L.s);
-            L.s = j + 1;  // samples s+1 .. j lie inside the empty cube
-            return 0;
-          }
-        }
-      }
-    } else {
-      DMF_RS(12, 1);
-    }
-#endif
     L.known_full = bl;  // occupied brick, or the jump failed: step through it
   }
   DMF_RS(3, 1);
@@ -478,9 +406,7 @@ __device__ inline bool rev_wave(const Geom& g, const DevVol& vd, const CamP& cam
             L.s = 0;
             L.known_full = 0xffffffffu;
             L.occi = 0xffffffffu;
-#if DMF_EXP_REV_PRECOMP
             L.pns = -1;
-#endif
             L.item = it;
             L.slot = slot;
             L.tz = t[2];
@@ -595,7 +521,7 @@ __global__ __launch_bounds__(256) void k_reverse_q(Geom g, DevVol vd, CamP cam, 
 // k_reverse_q), taken by the workgroup together: its waves share the CU's L1 lines as in
 // k_reverse_q, at the price of a barrier per unit; else one wave's 64 items per unit.
 template <int kItems, int kRefill, int kBurst, bool kWg>
-__global__ __launch_bounds__(256) DMF_REV_OCC void k_reverse_x(Geom g, DevVol vd, CamP cam, const PoseX* __restrict__ poses, int P,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kRevWaves))) void k_reverse_x(Geom g, DevVol vd, CamP cam, const PoseX* __restrict__ poses, int P,
                                                    int64_t nelem, const uint32_t* __restrict__ order, int depth0,
                                                    int max_steps, float dstar, int viz, uint64_t* __restrict__ vis_mask,
                                                    uint64_t* __restrict__ good_mask, int64_t words,
@@ -891,15 +817,11 @@ static int run_reverse(dmf_volume* v, const dmf_camera* cam, const float* poses,
     // the per-wave tail is the cost): 64 / 8 / 16 measured 5.54 ms vs 5.94 at 128 / 8 / 16 and
     // 6.51 at 512 / 8 / 8 (profiles/r04/reverse_queue_sweep.json)
     constexpr int kRevItems = 512, kRevRefill = 8, kRevBurst = 8;
-#if defined(DMF_EXP_REV_ITEMS)  // experiment builds: the spatial-order queue's shape
-    constexpr int kSpItems = DMF_EXP_REV_ITEMS, kSpRefill = DMF_EXP_REV_REFILL, kSpBurst = DMF_EXP_REV_BURST;
-#else
-    // (round 5, per-XCD queues: burst 32 5.24-5.25 ms vs 16 5.29-5.32, 24 5.25-5.26, 8 5.39-5.41;
+    // the spatial-order queue's shape (round 5, per-XCD queues: burst 32 5.24-5.25 ms vs 16 5.29-5.32, 24 5.25-5.26, 8 5.39-5.41;
     // refill 4 / 12 / 16 at burst 16 within +-0.5 %: profiles/r05j/.  Round 6, after the
     // unchecked jumps: burst 64 4.67-4.69 ms vs 32 4.71-4.72, 48 4.71-4.74, 96 4.68-4.70, 128 4.68;
     // refill 4 / 16 at burst 32 +-0.2 %: profiles/r06ab/, r06ac/)
     constexpr int kSpItems = 64, kSpRefill = 8, kSpBurst = 64;
-#endif
     const dim3 gridq((unsigned)((nelem + 4 * kRevItems - 1) / (4 * kRevItems)), (unsigned)P);
     const dim3 gridqs((unsigned)((nelem + 4 * kSpItems - 1) / (4 * kSpItems)), (unsigned)P);
     const Geom g = v->geom();
@@ -1094,21 +1016,10 @@ __device__ inline void fwd_ray(const Geom& g, const DevVol& vd, const CamP& cam,
           kj = min(kj, last_k);
           if (kj > k) {
             const int zj = zstart + kj * zdelta;
-#if DMF_FWD_VERIFY_JUMPS
-            float qc[3], q[3];
-            project(cam, r, c, zj, qc);
-            xform(m, qc[0], qc[1], qc[2], q);
-            ++samples;
-            if (!valid_points_f(g, q)) {  // verified: still outside
-              k = kj;
-              zd = zj;
-            }
-#else
             // zj is a whole step before the line enters the volume grown by the margin, so every
             // sample up to it is outside the volume: no sample is evaluated to check it
             k = kj;
             zd = zj;
-#endif
           }
         }
         continue;
@@ -1146,18 +1057,6 @@ __device__ inline void fwd_ray(const Geom& g, const DevVol& vd, const CamP& cam,
         if (kj > k + 1) {
           const int zj = zstart + kj * zdelta;
           bool ok = true;
-#if DMF_FWD_VERIFY_JUMPS
-          float qc[3], q[3];
-          project(cam, r, c, zj, qc);
-          xform(m, qc[0], qc[1], qc[2], q);
-          ++samples;
-#pragma unroll
-          for (int ax = 0; ax < 3; ++ax) {
-            const double dm = margin(ax, (double)zj);
-            ok = ok && (double)w[ax] >= lo[ax] + dm && (double)w[ax] <= hi[ax] - dm && (double)q[ax] >= lo[ax] + dm &&
-                 (double)q[ax] <= hi[ax] - dm;
-          }
-#else
           // sample j is not evaluated: the line's point at zj inside the cube shrunk by 2 delta
           // puts sample j inside it shrunk by delta (its rounding is within eps of the line)
 #pragma unroll
@@ -1166,7 +1065,6 @@ __device__ inline void fwd_ray(const Geom& g, const DevVol& vd, const CamP& cam,
             ok = ok && (double)w[ax] >= lo[ax] + dm && (double)w[ax] <= hi[ax] - dm && lq >= lo[ax] + 2.0 * dm &&
                  lq <= hi[ax] - 2.0 * dm;
           }
-#endif
           if (ok) {  // samples k+1 .. kj lie inside the empty cube
             k = kj;
             zd = zj;
@@ -1182,7 +1080,7 @@ __device__ inline void fwd_ray(const Geom& g, const DevVol& vd, const CamP& cam,
 }
 
 template <bool kSkip>
-__global__ __launch_bounds__(256) DMF_FWD_OCC void k_forward(Geom g, DevVol vd, CamP cam, const PoseX* __restrict__ pose,
+__global__ __launch_bounds__(256) void k_forward(Geom g, DevVol vd, CamP cam, const PoseX* __restrict__ pose,
                                                  int zstart, int zdelta, int rdelta, int cdelta, int R, int C,
                                                  int32_t* __restrict__ k_out, int32_t* __restrict__ slot_out,
                                                  unsigned long long* __restrict__ hazards,
@@ -1281,19 +1179,8 @@ __device__ inline int fwd_step(const Geom& g, const DevVol& vd, const CamP& cam,
       kj = min(kj, last_k);
       if (kj > L.k) {
         const int zj = zstart + kj * zdelta;
-#if DMF_FWD_VERIFY_JUMPS
-        float qc[3], q[3];
-        project(cam, r, c, zj, qc);
-        xform(m, qc[0], qc[1], qc[2], q);
-        ++samples;
-        if (!valid_points_f(g, q)) {
-          L.k = kj;
-          L.zd = zj;
-        }
-#else
         L.k = kj;  // (as fwd_ray)
         L.zd = zj;
-#endif
       }
     }
     L.zd += zdelta;
@@ -1336,25 +1223,12 @@ __device__ inline int fwd_step(const Geom& g, const DevVol& vd, const CamP& cam,
         if (kj > L.k + 1) {
           const int zj = zstart + kj * zdelta;
           bool ok = true;
-#if DMF_FWD_VERIFY_JUMPS
-          float qc[3], q[3];
-          project(cam, r, c, zj, qc);
-          xform(m, qc[0], qc[1], qc[2], q);
-          ++samples;
-#pragma unroll
-          for (int ax = 0; ax < 3; ++ax) {
-            const double dm = margin(ax, (double)zj);
-            ok = ok && (double)w[ax] >= lo[ax] + dm && (double)w[ax] <= hi[ax] - dm && (double)q[ax] >= lo[ax] + dm &&
-                 (double)q[ax] <= hi[ax] - dm;
-          }
-#else
 #pragma unroll
           for (int ax = 0; ax < 3; ++ax) {  // (as fwd_ray)
             const double dm = margin(ax, (double)zj), lq = (double)m[4 * ax + 3] + (double)zj * L.dir[ax];
             ok = ok && (double)w[ax] >= lo[ax] + dm && (double)w[ax] <= hi[ax] - dm && lq >= lo[ax] + 2.0 * dm &&
                  lq <= hi[ax] - 2.0 * dm;
           }
-#endif
           if (ok) {
             L.k = kj;
             L.zd = zj;
@@ -1375,7 +1249,7 @@ __device__ inline int fwd_step(const Geom& g, const DevVol& vd, const CamP& cam,
 // order: neighbouring rays together) when at least kRefill lanes are idle; between refills
 // every busy lane marches up to kBurst samples.
 template <bool kSkip, int kUnit, int kRefill, int kBurst>
-__global__ __launch_bounds__(256) DMF_FWDQ_OCC void k_forward_q(Geom g, DevVol vd, CamP cam,
+__global__ __launch_bounds__(256) void k_forward_q(Geom g, DevVol vd, CamP cam,
                                                                 const PoseX* __restrict__ pose, int zstart, int zdelta,
                                                                 int rdelta, int cdelta, int R, int C,
                                                                 int32_t* __restrict__ k_out, int32_t* __restrict__ slot_out,
@@ -1495,11 +1369,7 @@ __global__ __launch_bounds__(256) void k_forward_x(Geom g, DevVol vd, CamP cam, 
 }
 
 // k_forward_q's shape: tiles per wave unit, refill threshold, samples per burst
-#if defined(DMF_EXP_FWDQ_UNIT)
-constexpr int kFwdUnit = DMF_EXP_FWDQ_UNIT, kFwdRefill = DMF_EXP_FWDQ_REFILL, kFwdBurst = DMF_EXP_FWDQ_BURST;
-#else
 constexpr int kFwdUnit = 4, kFwdRefill = 16, kFwdBurst = 8;
-#endif
 
 // threads of a k_forward launch per pose: whole 8x8 tiles of the R x C lattice
 static unsigned fwd_blocks(int R, int C) {

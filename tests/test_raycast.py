@@ -143,7 +143,7 @@ def test_reference_walks_the_fusion_cells(oracle):
 
 # ---------------------------------------------------------------- the exact jump's arithmetic
 def _jump_setup(n, rnd):
-    """dda_setup's walk state (csrc/dmf_fuse.hip) for random quantised endpoints in an n grid."""
+    """dda_setup's walk state (csrc/dmf_dda.hpp) for random quantised endpoints in an n grid."""
     Q, never = 256, 1 << 30
     qs = [rnd.randrange(0, n[a] * Q) for a in range(3)]
     qe = [rnd.randrange(0, n[a] * Q) for a in range(3)]
@@ -177,7 +177,7 @@ def _select(E, K):
 
 
 def _jump(m, c, st, E, K):
-    """rc_jump (csrc/dmf_fuse.hip) restated: -> (steps, cell after, E after)."""
+    """rc_jump (csrc/dmf_raycast.hip) restated: -> (steps, cell after, E after)."""
     def before(d, rs, kb, ka, after):
         x = d + rs * kb
         if x < 0 or ka == 0:

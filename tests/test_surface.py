@@ -94,13 +94,13 @@ int main() {
 
 @pytest.mark.timeout(900)
 def test_surface_kernels_no_scratch_no_spills(tmp_path):
-    """tests/test_kernel_resources.py's check for csrc/dmf_surface.hip: the four kernels keep their
-    state in registers, and the streaming and bit passes stay light enough for full occupancy."""
+    """Stricter than tests/test_kernel_resources.py's check of every source, for csrc/dmf_surface.hip:
+    the four kernels exist, spill no SGPR either, and the streaming and bit passes stay light enough
+    for full occupancy."""
     import test_kernel_resources as KR
     if not os.path.exists(KR.HIPCC):
         pytest.skip("hipcc not installed")
-    ks = {n: v for n, v in KR._kernels(os.path.join(KR.PKG, "csrc", "dmf_surface.hip"), tmp_path).items()
-          if n.startswith("_ZN3dmf")}
+    ks = {n: v for n, v in KR._kernels("dmf_surface", tmp_path).items() if n.startswith("_ZN3dmf")}
     for name in ("k_sf_mask", "k_sf_surface", "k_sf_totals", "k_sf_emit"):
         assert any(name in n for n in ks), (name, sorted(ks))
     bad = {n: v for n, v in ks.items() if v.get("private_segment_fixed_size", 0) or v.get("vgpr_spill_count", 0)

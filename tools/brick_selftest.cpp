@@ -73,7 +73,7 @@ static void fine_walk(const int64_t qs[3], const int64_t qe[3], std::vector<Cell
   out.push_back({(int)cur[0], (int)cur[1], (int)cur[2]});
 }
 
-// The kernels' int32 walk (dmf_fuse.hip dda_select) restarted from crossing counts c.
+// The kernels' int32 walk (dmf_dda.hpp dda_select) restarted from crossing counts c.
 static void restart_walk(const QRay& r, const int32_t c[3], int cells, std::vector<Cell>& out) {
   const uint32_t K[3] = {(uint32_t)(2 * kQ * r.adq[0]), (uint32_t)(2 * kQ * r.adq[1]), (uint32_t)(2 * kQ * r.adq[2])};
   int32_t E01 = (int32_t)((uint32_t)e0_pair(r, 0, 1) + (uint32_t)c[0] * K[1] - (uint32_t)c[1] * K[0]);

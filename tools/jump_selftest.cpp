@@ -1,5 +1,5 @@
-// CPU self-test of the reverse march's unchecked empty-space jumps (csrc/dmf_trace.hip rev_step
-// with DMF_REV_VERIFY_JUMPS = 0): from a sample s inside an empty cube of bricks
+// CPU self-test of the reverse march's unchecked empty-space jumps (csrc/dmf_trace.hip rev_step,
+// DESIGN.md §5.5): from a sample s inside an empty cube of bricks
 // (radius R around the sample's brick, clipped to the grid), the target j is computed from the
 // cube's exit faces moved toward the sample by Geom::jmarg, in the kernel's float arithmetic;
 // the march then continues at j without evaluating it first.  Exactness needs sample j inside
@@ -64,7 +64,7 @@ static bool valid_f(const Geom& g, const float p[3]) {
   return true;
 }
 
-// ---- forward march (csrc/dmf_trace.hip fwd_ray / fwd_step, DMF_FWD_VERIFY_JUMPS = 0) ------
+// ---- forward march (csrc/dmf_trace.hip fwd_ray / fwd_step) -------------------------------
 // Sample k of lattice pixel (r, c): w = T * projectPoint(r, c, zd_k) in the reference's
 // arithmetic (Camera.hpp:24-31 in double, narrowed to float; Eigen's Affine3f product with the
 // a0 + (a1 + a2) reduction).  A brick jump to sample j is taken without evaluating it when the
@@ -303,7 +303,7 @@ int main(int argc, char** argv) {
             clo[a] = std::max(bx[a] - R, 0) << bsh;
             chi[a] = std::min((bx[a] + R + 1) << bsh, g.n[a]);
             if (v[a] == 0.0f) continue;
-            // rev_step (DMF_REV_VERIFY_JUMPS = 0): the exit face moved in by jmarg
+            // rev_step: the exit face moved in by jmarg
             const int cf = v[a] > 0.0f ? chi[a] : clo[a];
             const float face = (float)(g.mn[a] + (double)cf * g.dl[a]);
             const float fin = v[a] > 0.0f ? face - g.jmarg[a] : face + g.jmarg[a];
