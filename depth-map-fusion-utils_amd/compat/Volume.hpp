@@ -148,6 +148,32 @@ class VoxelVolume {
     return (long long)n;
   }
 
+  // Distance field of a fused log-odds grid (dmf_grid_distance; not in the
+  // reference): out[(x * ydim_ + y) * zdim_ + z] = the squared distance, in cells, to the nearest
+  // cell with L >= threshold; DMF_NO_DIST everywhere when there is none.
+  void distanceField(const std::vector<int16_t>& L, int threshold, std::vector<uint32_t>& out) {
+    if (L.size() != (size_t)xdim_ * ydim_ * zdim_) throw std::invalid_argument("distanceField: grid size");
+    out.assign(L.size(), 0);
+    dmf_check(dmf_grid_distance(h_, L.data(), threshold, out.data(), nullptr));
+  }
+  // The least dist2 over the cells of each segment a[i] -> b[i] (the cells the ray origin a[i],
+  // point b[i] updates in the point fusion); DMF_NO_DIST for a segment that visits no cell.
+  std::vector<uint32_t> segmentClearance(const std::vector<uint32_t>& dist2, const std::vector<Eigen::Vector3f>& a,
+                                         const std::vector<Eigen::Vector3f>& b) {
+    if (dist2.size() != (size_t)xdim_ * ydim_ * zdim_) throw std::invalid_argument("segmentClearance: field size");
+    if (a.size() != b.size()) throw std::invalid_argument("segmentClearance: a and b differ in length");
+    std::vector<float> pa(3 * a.size()), pb(3 * b.size());
+    for (size_t i = 0; i < a.size(); ++i)
+      for (int k = 0; k < 3; ++k) {
+        pa[3 * i + k] = a[i](k);
+        pb[3 * i + k] = b[i](k);
+      }
+    std::vector<uint32_t> out(a.size(), 0);
+    if (!a.empty())
+      dmf_check(dmf_grid_clearance(h_, dist2.data(), pa.data(), pb.data(), (int64_t)a.size(), out.data()));
+    return out;
+  }
+
   // Volume.hpp:235-255 (with the reference's `i==j==k==0` test)
   std::vector<unsigned long long int> getNeighborHashes(unsigned long long int hash, int K = 1) {
     int x, y, z;

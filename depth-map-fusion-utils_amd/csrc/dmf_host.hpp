@@ -65,7 +65,9 @@ enum ScratchSlot {
   kScRcFine, kScRcCoarse,  // the log-odds ray-cast's solid mask and its tile + brick levels (dmf_raycast.hip)
   // surface extraction (dmf_surface.hip): the solid, free and surface masks, the per-row counts
   // and their scan, the {surface, solid} counters, and the host forms' output staging
-  kScSfSolid, kScSfFree, kScSfSurf, kScSfCounts, kScSfBases, kScSfTotals, kScSfHash, kScSfXyz, kScSfNrm
+  kScSfSolid, kScSfFree, kScSfSurf, kScSfCounts, kScSfBases, kScSfTotals, kScSfHash, kScSfXyz, kScSfNrm,
+  // the distance field (dmf_distance.hip): the y / x passes' envelope stacks, and the host forms' field
+  kScDfStack, kScDfDist
 };
 
 // Striped statistics: kernels add into slot (block % kStatSlots) of a zeroed buffer

@@ -31,6 +31,9 @@ __all__ = ["Camera", "VoxelVolume", "RayTracingEngine", "OccupancyGrid", "DmfErr
 # RayTracingEngine.raycast_logodds: the cell value of a pixel whose ray finds no solid cell
 # (DMF_NO_CELL, include/dmf.h; no getHashId is all ones)
 NO_CELL = np.uint64(0xFFFFFFFFFFFFFFFF)
+# VoxelVolume.distance_field / segment_clearance: no solid cell in the grid / no cell on the segment
+# (DMF_NO_DIST, include/dmf.h; no squared distance in a grid of at most 2048 cells per axis is all ones)
+NO_DIST = np.uint32(0xFFFFFFFF)
 
 
 def degree(radian):
@@ -255,6 +258,42 @@ class VoxelVolume:
         check(self._L.dmf_volume_integrate_surface(self._h, ptr(lo), int(occ_threshold), int(free_threshold),
                                                    C.addressof(n)))
         return n.value
+
+    # -- distance field of a fused log-odds grid and segment clearance, on the GPU
+    def distance_field(self, logodds, threshold=1):
+        """The exact squared Euclidean distance field of the int16 log-odds grid `logodds`
+        (xdim*ydim*zdim cells, x-major, as fuse_finalize returns it) -> uint32 (xdim, ydim, zdim):
+        per cell the least (x-x')^2 + (y-y')^2 + (z-z')^2 over the solid cells (log-odds >=
+        threshold), 0 on solid cells, NO_DIST everywhere when no cell is solid.  Threshold 1 makes
+        the observed-occupied cells the obstacles; 0 also counts unobserved cells (conservative).
+        The unit is the cell index, so the field is exact for every volume: with cubic voxels the
+        distance in metres is sqrt(d2) * delta, with anisotropic ones sqrt(d2) * min(delta) is a
+        lower bound.  The volume's point-cloud occupancy is not touched."""
+        lo = self._logodds(logodds)
+        out = np.empty(tuple(self.dims), np.uint32)
+        check(self._L.dmf_grid_distance(self._h, ptr(lo), int(threshold), ptr(out), None))
+        return out
+
+    def segment_clearance(self, dist2, a, b):
+        """The clearance of the segments a[i] -> b[i] (float32 world-frame points, (n, 3) or (3,)) in
+        the field `dist2` of distance_field (uint32, xdim*ydim*zdim cells) -> uint32 (n,): the
+        minimum of dist2 over the cells the ray with origin a[i] and endpoint b[i] updates in
+        fuse_points (only the part inside the grid); NO_DIST for a segment that visits no cell (a
+        non-finite coordinate, or it misses the grid).  A body of radius r cells collides on
+        segment i iff the result is < r * r."""
+        n = int(np.prod(self.dims))
+        d2 = np.asarray(dist2)
+        if d2.dtype != np.uint32 or d2.size != n:
+            raise ValueError(f"dist2 must be uint32 with {n} cells (x-major over dims {tuple(self.dims)}), "
+                             f"got {d2.dtype} with {d2.size}")
+        d2 = np.ascontiguousarray(d2).reshape(-1)
+        pa, pb = (np.ascontiguousarray(p, np.float32) for p in (a, b))
+        if pa.shape != pb.shape or pa.ndim not in (1, 2) or pa.shape[-1] != 3:
+            raise ValueError(f"a and b must both be (n, 3) or (3,), got {pa.shape} and {pb.shape}")
+        pa, pb = pa.reshape(-1, 3), pb.reshape(-1, 3)
+        out = np.empty(pa.shape[0], np.uint32)
+        check(self._L.dmf_grid_clearance(self._h, ptr(d2), ptr(pa), ptr(pb), pa.shape[0], ptr(out)))
+        return out
 
     @property
     def occupied_cells_(self):

@@ -134,6 +134,10 @@ SIGNATURES = {
     "dmf_grid_surface_device": (C.c_int, [_vp, _p, _i32, _i32, _p, _p, _p, _i64, _p]),
     "dmf_grid_surface": (C.c_int, [_vp, _p, _i32, _i32, _p, _p, _p, _i64, _p, _p]),
     "dmf_volume_integrate_surface": (C.c_int, [_vp, _p, _i32, _i32, _p]),
+    "dmf_grid_distance": (C.c_int, [_vp, _p, _i32, _p, _p]),
+    "dmf_grid_distance_device": (C.c_int, [_vp, _p, _i32, _p, _p]),
+    "dmf_grid_clearance": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
+    "dmf_grid_clearance_device": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
     "dmf_fuse_counter_cells": (C.c_int, [_vp, _p]),
     "dmf_fuse_counters_to_linear_device": (C.c_int, [_vp, _p, _p]),
     "dmf_fuse_reserve": (C.c_int, [_vp, _p, _i32, C.c_uint64]),

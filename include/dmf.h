@@ -413,6 +413,45 @@ int dmf_grid_surface(dmf_volume* v, const int16_t* logodds, int32_t occ_threshol
 int dmf_volume_integrate_surface(dmf_volume* v, const int16_t* logodds, int32_t occ_threshold,
                                  int32_t free_threshold, int64_t* n);
 
+/* Exact squared Euclidean distance field of a fused log-odds grid: for every
+ * cell of `logodds` (int16, x-major over xdim*ydim*zdim, as dmf_fuse_finalize* writes it) how far
+ * the nearest obstacle is.  A cell is solid iff its log-odds >= threshold (any int32), as in the
+ * ray-cast: threshold 1 makes the observed-occupied cells the obstacles, threshold 0 also counts
+ * every unobserved cell, which suits a conservative planner.
+ *   dist2[x][y][z] (uint32, x-major like the grid) = the minimum over the solid cells (x', y', z')
+ *   of (x-x')^2 + (y-y')^2 + (z-z')^2, exactly: 0 on solid cells, DMF_NO_DIST on every cell when
+ *   the grid has no solid cell; there is no cap and no truncation radius.
+ * The unit is the CELL INDEX, not the metre, so the field is an exact integer for every volume.
+ * For cubic voxels (the reference drivers size all axes at 125 voxels/m) the distance in metres
+ * is sqrtf(dist2) * delta; for anisotropic voxels sqrtf(dist2) * min(delta) is a lower bound.
+ * Only the volume's geometry (its dims) is used; its point-cloud occupancy is neither read nor
+ * changed.  Host form: host pointers, synchronises; n_solid (may be NULL) = the solid cells.
+ * Device form: device pointers, only enqueues on the volume's stream, allocates only when its
+ * scratch (8 B per cell) must grow and reuses it on later calls; d_dist2 is also the passes'
+ * intermediate; d_count (may be NULL): 1 counter = the solid cells.
+ * Null v / grid / dist2 are DMF_ERR_INVALID (checked before the volume is touched); an
+ * unconstructed volume is DMF_ERR_STATE; more than 2048 cells on an axis is DMF_ERR_RANGE.
+ *
+ * Clearance of path segments, the planner's query: a[n][3] and b[n][3] are float32 world-frame
+ * points, dist2 a field of this volume.  clear2[i] = the minimum of dist2 over the cells that the
+ * ray with origin a[i] and endpoint b[i] updates in the point fusion above (every cell that would
+ * receive a miss, or the hit: the same endpoint acceptance, clip, 1/256-cell quantisation and
+ * integer DDA with ties x < y < z).  Only the part of a segment inside the grid is examined; a
+ * segment with a non-finite coordinate, or one that misses the grid, visits no cell and gives
+ * DMF_NO_DIST.  The caller compares clear2 with its own radius^2 in cells: a body of radius r cells
+ * collides on the segment iff clear2 < r^2.  Null pointers and n < 0 are DMF_ERR_INVALID; n = 0 is
+ * DMF_OK and touches nothing; the volume is checked as above.  Host form: host pointers,
+ * synchronises.  Device form: device pointers, only enqueues on the volume's stream. */
+#define DMF_NO_DIST UINT32_MAX
+int dmf_grid_distance(dmf_volume* v, const int16_t* logodds, int32_t threshold, uint32_t* dist2,
+                      int64_t* n_solid);
+int dmf_grid_distance_device(dmf_volume* v, const int16_t* d_logodds, int32_t threshold, uint32_t* d_dist2,
+                             uint64_t* d_count);
+int dmf_grid_clearance(dmf_volume* v, const uint32_t* dist2, const float* a, const float* b, int64_t n,
+                       uint32_t* clear2);
+int dmf_grid_clearance_device(dmf_volume* v, const uint32_t* d_dist2, const float* d_a, const float* d_b,
+                              int64_t n, uint32_t* d_clear2);
+
 /* ---- multi-GPU merge over RCCL ------------------------
  * Poses shard across ranks, each rank fuses into its own replica of the counters, and
  * the replicas merge with integer collectives (bit-identical to one rank fusing all
