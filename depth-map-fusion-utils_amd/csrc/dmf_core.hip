@@ -40,6 +40,12 @@ int require_constructed(const dmf_volume* v) {
   return activate(v);
 }
 
+int require_grid_2048(const dmf_volume* v, const char* text) {
+  DMF_TRY(require_constructed(v));
+  if (v->xdim > 2048 || v->ydim > 2048 || v->zdim > 2048) return fail(DMF_ERR_RANGE, "%s", text);
+  return DMF_OK;
+}
+
 int scratch(dmf_volume* v, int k, size_t bytes, void** out) {
   if ((int)v->scratch.size() <= k) v->scratch.resize(k + 1, {nullptr, 0});
   auto& s = v->scratch[k];
@@ -57,6 +63,12 @@ int scratch(dmf_volume* v, int k, size_t bytes, void** out) {
     s.second = nb;
   }
   *out = s.first;
+  return DMF_OK;
+}
+
+int upload_grid(dmf_volume* v, const int16_t* logodds, void** d_grid) {
+  DMF_TRY(scratch(v, kScOut2, sizeof(int16_t) * v->ncell, d_grid));
+  DMF_HIP(hipMemcpyAsync(*d_grid, logodds, sizeof(int16_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
   return DMF_OK;
 }
 
@@ -189,13 +201,10 @@ __global__ void k_mask_popc(const uint64_t* __restrict__ m, int64_t n, int64_t* 
 
 // centroid hash of enumeration entry e (RayTracingEngine.hpp:66,74): getHash(x+dx/2, ...)
 __device__ inline uint64_t enum_centroid_hash(const Geom& g, const float* axes, const int32_t* nax, uint32_t e) {
-  const uint32_t nyz = (uint32_t)nax[1] * (uint32_t)nax[2];
-  const uint32_t i = e / nyz, j = (e / nax[2]) % nax[1], k = e % nax[2];
-  const float x = axes[i], y = axes[nax[0] + j], z = axes[nax[0] + nax[1] + k];
-  const float cx = (float)((double)x + g.hdl[0]);
-  const float cy = (float)((double)y + g.hdl[1]);
-  const float cz = (float)((double)z + g.hdl[2]);
-  return hash_id(bin_axis(g, 0, cx), bin_axis(g, 1, cy), bin_axis(g, 2, cz));
+  float x, y, z, cen[3];
+  enum_xyz(axes, nax, e, &x, &y, &z);
+  centre_of_corner(g, x, y, z, cen);
+  return hash_id(bin_axis(g, 0, cen[0]), bin_axis(g, 1, cen[1]), bin_axis(g, 2, cen[2]));
 }
 
 struct EnumCtx {

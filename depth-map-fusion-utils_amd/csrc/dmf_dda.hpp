@@ -1,7 +1,7 @@
 // dmf_dda.hpp — the exact integer 3D-DDA of a probe ray and the tiled counter
-// layout, shared by the fusion kernels (dmf_fuse.hip) and the log-odds ray-cast
-// (dmf_raycast.hip): clip and quantise camera centre -> endpoint, the int32 walk state, one
-// selection step, and the per-pixel ray of a depth frame.
+// layout, shared by the fusion kernels (dmf_fuse.hip), the log-odds ray-cast (dmf_raycast.hip)
+// and the segment clearance (dmf_distance.hip): clip and quantise origin -> endpoint, the int32
+// walk state, one selection step, the walk in scalars, and the per-pixel ray of a depth frame.
 #pragma once
 #include "dmf_internal.hpp"
 
@@ -74,6 +74,25 @@ __device__ inline void dda_select(int32_t& E01, int32_t& E02, int32_t& E12, int3
   E02 += s0 ? K2 : (s2 ? -K0 : 0);
   E12 += s1 ? K2 : (s2 ? -K1 : 0);
 }
+
+// A Ray's walk in scalars: a lane keeps it in registers (members, never arrays indexed by an axis:
+// a dynamically indexed private array once made phase F 15x slower).  left counts the cells still
+// to visit, the current one included; the caller owns its decrement.
+struct Walk {
+  int c0, c1, c2, st0, st1, st2;
+  int32_t E01, E02, E12, K0, K1, K2;
+  int left;
+  __device__ explicit Walk(const Ray& R)
+      : c0(R.c[0]), c1(R.c[1]), c2(R.c[2]), st0(R.st[0]), st1(R.st[1]), st2(R.st[2]), E01(R.E01), E02(R.E02),
+        E12(R.E12), K0(R.K[0]), K1(R.K[1]), K2(R.K[2]), left(R.left) {}
+  __device__ void step() {  // to the next cell of the sequence
+    bool s0, s1, s2;
+    dda_select(E01, E02, E12, K0, K1, K2, s0, s1, s2);
+    c0 += s0 ? st0 : 0;
+    c1 += s1 ? st1 : 0;
+    c2 += s2 ? st2 : 0;
+  }
+};
 
 // (x - min) / delta in double (oracle.cpp dda_ray); a power-of-two delta divides exactly
 // as a multiplication by its (exact) reciprocal, as in bin_axis

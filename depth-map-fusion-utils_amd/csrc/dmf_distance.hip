@@ -3,7 +3,8 @@
 // (x-x')^2 + (y-y')^2 + (z-z')^2 over the solid cells (L >= threshold), in cell-index units, by a
 // separable transform in integers (Felzenszwalb & Huttenlocher's lower envelope of parabolas):
 //  k_df_z     — one streaming pass over the grid.  A workgroup takes whole (x, y) rows, up to
-//               kDfZCells contiguous cells: 16-B loads make the rows' solid bits in LDS, a wave scan
+//               kDfZCells contiguous cells: 16-B loads (for_cells8, dmf_gridbits.hpp) make the rows'
+//               solid bits in LDS, a wave scan
 //               over the words gives every word the nearest set bit before and after it, and each
 //               cell's squared distance to the nearest solid cell OF ITS ROW (clz / ctz in its own
 //               word, else the word's neighbours, cut at the row's ends) is stored 16 B per lane.
@@ -19,7 +20,7 @@
 //               finite site is left as it is, infinite for the next pass.  kDfInf = DMF_NO_DIST, so
 //               what is still infinite after the last pass already is the result;
 //  k_df_clear — one lane per segment: the fusion's own ray (endpoint acceptance, clip, quantisation,
-//               dda_setup and dda_select of dmf_dda.hpp), the minimum of dist2 over its cells.
+//               dda_setup and the Walk of dmf_dda.hpp), the minimum of dist2 over its cells.
 // All arithmetic is int32 / uint32: d^2 <= 3 * 2047^2 < 2^24, and a separator's numerator
 // f(q) + q^2 - f(v) - v^2 stays below 2^25 in magnitude.
 #include "dmf_dda.hpp"
@@ -55,21 +56,11 @@ __global__ __launch_bounds__(kDfZThreads) void k_df_z(int64_t ncell, int nz, int
   if (i < kDfZWords) bits[i] = 0;
   if (i == 0) scount = 0;
   __syncthreads();
-  const bool aligned = ((uintptr_t)L & 15) == 0;
   for (int j = i; j < ngroups; j += kDfZThreads) {
     const int64_t p = a0 + 8 * (int64_t)j;
     uint32_t b = 0;
-    if (aligned && p + 8 <= ncell) {
-      const uint4 q = *(const uint4*)(L + p);
-      const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        b |= (uint32_t)((int)(int16_t)(u[k] & 0xffffu) >= threshold) << (2 * k);
-        b |= (uint32_t)((int)(int16_t)(u[k] >> 16) >= threshold) << (2 * k + 1);
-      }
-    } else {
-      for (int k = 0; k < 8 && p + k < ncell; ++k) b |= (uint32_t)((int)L[p + k] >= threshold) << k;
-    }
+    for_cells8(L + p, (int)(ncell - p < 8 ? ncell - p : 8),
+               [&](int k, int c) { b |= (uint32_t)(c >= threshold) << k; });
     ((unsigned char*)bits)[j] = (unsigned char)b;
   }
   __syncthreads();
@@ -263,19 +254,10 @@ __global__ __launch_bounds__(kDfClearThreads) void k_df_clear(Geom g, const uint
   uint32_t best = kDfInf;
   Ray R = {};
   if (df_finite3(O) && df_finite3(E) && !dda_setup(g, O, E, endpoint_inside(g, E), R)) R.left = 0;
-  int32_t E01 = R.E01, E02 = R.E02, E12 = R.E12;
-  const int32_t K0 = R.K[0], K1 = R.K[1], K2 = R.K[2];
-  const int st0 = R.st[0], st1 = R.st[1], st2 = R.st[2];
-  int c0 = R.c[0], c1 = R.c[1], c2 = R.c[2], left = R.left;
-  while (left > 0) {
-    const uint32_t d = dist2[((int64_t)c0 * g.n[1] + c1) * g.n[2] + c2];
+  for (Walk W(R); W.left > 0; W.step()) {
+    const uint32_t d = dist2[((int64_t)W.c0 * g.n[1] + W.c1) * g.n[2] + W.c2];
     best = d < best ? d : best;
-    if (--left == 0) break;
-    bool s0, s1, s2;
-    dda_select(E01, E02, E12, K0, K1, K2, s0, s1, s2);
-    c0 += s0 ? st0 : 0;
-    c1 += s1 ? st1 : 0;
-    c2 += s2 ? st2 : 0;
+    if (--W.left == 0) break;
   }
   clear2[i] = best;
 }
@@ -291,12 +273,7 @@ static int check_clearance_args(const dmf_volume* v, const void* dist2, const vo
   if (n < 0) return fail(DMF_ERR_INVALID, "negative segment count %lld", (long long)n);
   return DMF_OK;
 }
-static int check_distance_volume(const dmf_volume* v) {
-  DMF_TRY(require_constructed(v));
-  if (v->xdim > 2048 || v->ydim > 2048 || v->zdim > 2048)
-    return fail(DMF_ERR_RANGE, "the distance field is limited to 2048 cells per axis");
-  return DMF_OK;
-}
+static const char kDfGridLimit[] = "the distance field is limited to 2048 cells per axis";
 
 static int distance_device(dmf_volume* v, const int16_t* d_logodds, int32_t threshold, uint32_t* d_dist2,
                            uint64_t* d_count) {
@@ -343,7 +320,7 @@ int dmf_grid_distance_device(dmf_volume* v, const int16_t* d_logodds, int32_t th
                              uint64_t* d_count) {
   DMF_API_BEGIN
   DMF_TRY(check_distance_args(v, d_logodds, d_dist2));
-  DMF_TRY(check_distance_volume(v));
+  DMF_TRY(require_grid_2048(v, kDfGridLimit));
   return distance_device(v, d_logodds, threshold, d_dist2, d_count);
   DMF_API_END
 }
@@ -351,13 +328,12 @@ int dmf_grid_distance_device(dmf_volume* v, const int16_t* d_logodds, int32_t th
 int dmf_grid_distance(dmf_volume* v, const int16_t* logodds, int32_t threshold, uint32_t* dist2, int64_t* n_solid) {
   DMF_API_BEGIN
   DMF_TRY(check_distance_args(v, logodds, dist2));
-  DMF_TRY(check_distance_volume(v));
+  DMF_TRY(require_grid_2048(v, kDfGridLimit));
   void *dl, *dd, *dc;
   uint64_t cnt = 0;
-  DMF_TRY(scratch(v, kScOut2, sizeof(int16_t) * v->ncell, &dl));
+  DMF_TRY(upload_grid(v, logodds, &dl));
   DMF_TRY(scratch(v, kScDfDist, sizeof(uint32_t) * v->ncell, &dd));
   DMF_TRY(scratch(v, kScOut3, sizeof(uint64_t), &dc));
-  DMF_HIP(hipMemcpyAsync(dl, logodds, sizeof(int16_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
   DMF_TRY(distance_device(v, (const int16_t*)dl, threshold, (uint32_t*)dd, (uint64_t*)dc));
   DMF_HIP(hipMemcpyAsync(dist2, dd, sizeof(uint32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
   DMF_HIP(hipMemcpyAsync(&cnt, dc, sizeof(uint64_t), hipMemcpyDeviceToHost, v->stream));
@@ -372,7 +348,7 @@ int dmf_grid_clearance_device(dmf_volume* v, const uint32_t* d_dist2, const floa
   DMF_API_BEGIN
   DMF_TRY(check_clearance_args(v, d_dist2, d_a, d_b, n, d_clear2));
   if (n == 0) return DMF_OK;
-  DMF_TRY(check_distance_volume(v));
+  DMF_TRY(require_grid_2048(v, kDfGridLimit));
   return clearance_device(v, d_dist2, d_a, d_b, n, d_clear2);
   DMF_API_END
 }
@@ -382,7 +358,7 @@ int dmf_grid_clearance(dmf_volume* v, const uint32_t* dist2, const float* a, con
   DMF_API_BEGIN
   DMF_TRY(check_clearance_args(v, dist2, a, b, n, clear2));
   if (n == 0) return DMF_OK;
-  DMF_TRY(check_distance_volume(v));
+  DMF_TRY(require_grid_2048(v, kDfGridLimit));
   void *dd, *da, *db, *dc;
   const size_t nb = sizeof(float) * 3 * (size_t)n;
   DMF_TRY(scratch(v, kScDfDist, sizeof(uint32_t) * v->ncell, &dd));

@@ -2237,13 +2237,14 @@ int tile_rows(const dmf_volume* v, int64_t* ntx, int64_t* tiles_per_row) {
 
 static const dmf_fuse_params kDefaultParamsForCheck = {200, 1000, 847, -405, -2000, 3511};
 
+static const char kFuseGridLimit[] = "fusion grid is limited to 2048 cells per axis (fixed-point DDA)";
+
 static int check_fuse(const dmf_volume* v, const dmf_camera* cam, int P, const dmf_fuse_params* prm) {
-  DMF_TRY(require_constructed(v));
+  DMF_TRY(require_constructed(v));  // (before the camera: an unconstructed volume is reported first)
   DMF_TRY(check_camera(cam));
   if (!prm) return fail(DMF_ERR_INVALID, "null params");
   if (P <= 0 || P > 65535) return fail(DMF_ERR_INVALID, "pose count %d out of range [1,65535]", P);
-  if (v->xdim > 2048 || v->ydim > 2048 || v->zdim > 2048)
-    return fail(DMF_ERR_RANGE, "fusion grid is limited to 2048 cells per axis (fixed-point DDA)");
+  DMF_TRY(require_grid_2048(v, kFuseGridLimit));
   if (tiled_cells(v->geom().n) > (size_t)UINT32_MAX)
     return fail(DMF_ERR_RANGE, "fusion grid is limited to 2^32 tiled counter cells");
   return DMF_OK;
@@ -2262,9 +2263,7 @@ static int check_fuse_points(const dmf_volume* v, int S, int64_t N, const dmf_fu
   if (!prm) return fail(DMF_ERR_INVALID, "null params");
   if (N < 1) return fail(DMF_ERR_INVALID, "point count %lld per scan must be >= 1", (long long)N);
   if (S <= 0 || S > 65535) return fail(DMF_ERR_INVALID, "scan count %d out of range [1,65535]", S);
-  DMF_TRY(require_constructed(v));
-  if (v->xdim > 2048 || v->ydim > 2048 || v->zdim > 2048)
-    return fail(DMF_ERR_RANGE, "fusion grid is limited to 2048 cells per axis (fixed-point DDA)");
+  DMF_TRY(require_grid_2048(v, kFuseGridLimit));
   if (tiled_cells(v->geom().n) > (size_t)UINT32_MAX)
     return fail(DMF_ERR_RANGE, "fusion grid is limited to 2^32 tiled counter cells");
   if (N > (int64_t)INT32_MAX - 63) return fail(DMF_ERR_RANGE, "one frame exceeds the 32-bit pair offsets");

@@ -77,6 +77,20 @@ __host__ __device__ inline int bin_axis(const Geom& g, int a, float x) {
   return (int)floor(q);
 }
 
+// The voxel centre as the reference forms it in float (RayTracingEngine.hpp:157, :66):
+// centroid = f32(f64(x) + delta/2) of a voxel's corner x ...
+__host__ __device__ inline void centre_of_corner(const Geom& g, float x, float y, float z, float cen[3]) {
+  cen[0] = (float)((double)x + g.hdl[0]);
+  cen[1] = (float)((double)y + g.hdl[1]);
+  cen[2] = (float)((double)z + g.hdl[2]);
+}
+// ... and the corner of cell (i, j, k) as reverseRayTraceFast forms it (:151-153):
+// x = f32(f64(i) * delta + min).
+__host__ __device__ inline void cell_centre(const Geom& g, int i, int j, int k, float cen[3]) {
+  centre_of_corner(g, (float)((double)i * g.dl[0] + g.mn[0]), (float)((double)j * g.dl[1] + g.mn[1]),
+                   (float)((double)k * g.dl[2] + g.mn[2]), cen);
+}
+
 // bin_axis from the float estimate: true (and *out = the bin) when certified (fbin_setup);
 // false when the estimate is too close to a cell boundary -- then bin_axis decides.
 __host__ __device__ inline bool bin_axis_f(const Geom& g, int a, float x, int* out) {

@@ -44,9 +44,13 @@ int fail(int status, const char* fmt, ...);
 int activate(const dmf_volume* v);
 inline dmf_volume* v_mut(const dmf_volume* v) { return const_cast<dmf_volume*>(v); }
 int require_constructed(const dmf_volume* v);
+// ... and at most 2048 cells per axis (the fixed-point DDA's limit), else DMF_ERR_RANGE with `text`
+int require_grid_2048(const dmf_volume* v, const char* text);
 
 // Scratch arena: slot k is a device buffer grown on demand, reused across calls.
 int scratch(dmf_volume* v, int k, size_t bytes, void** out);
+// The fused grid's consumers, host forms: the caller's int16 grid into slot kScOut2 (on the stream).
+int upload_grid(dmf_volume* v, const int16_t* logodds, void** d_grid);
 enum ScratchSlot {
   kScPoses = 0, kScHost0, kScHost1, kScHost2, kScOut0, kScOut1, kScOut2, kScOut3, kScTmp, kScSort0,
   kScSort1, kScSort2, kScSort3, kScCount, kScStats,

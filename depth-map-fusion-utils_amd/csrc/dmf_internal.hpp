@@ -17,6 +17,7 @@
 #include "dmf.h"
 #include "dmf_diag.h"
 #include "dmf_geom.hpp"
+#include "dmf_gridbits.hpp"
 
 namespace dmf {
 
@@ -130,20 +131,27 @@ __host__ __device__ inline uint64_t hash_id(int x, int y, int z) {
   return ((uint64_t)(int64_t)x << 40) ^ (uint64_t)(int64_t)(y << 20) ^ (uint64_t)(int64_t)z;
 }
 
-// Occupancy bitmask layout: 8x8x8-cell tiles of 512 bits (16 words = 64 B), tiles x-major
-// over the grid padded to whole tiles, bit (x&7)*64 + (y&7)*8 + (z&7) inside a tile.  A
-// march sample stays in one tile for several samples whatever the ray direction; with
-// x-major bits (one 128-B line = 1024 z-cells of one (x, y) column) a reverse march left
-// the line at nearly every sample: L2 hit rate 0.50 and 43 GB beyond L2 per 128-pose
+// Entry e = (i * ny + j) * nz + k of the float-accumulated enumeration (RayTracingEngine.hpp:54-56)
+// -> its x, y, z from the axes table xs | ys | zs (dmf_volume::d_axes, nax).
+__device__ inline void enum_xyz(const float* axes, const int32_t nax[3], uint32_t e, float* x, float* y, float* z) {
+  const uint32_t nyz = (uint32_t)nax[1] * (uint32_t)nax[2];
+  const uint32_t i = e / nyz, j = (e / nax[2]) % nax[1], k = e % nax[2];
+  *x = axes[i];
+  *y = axes[nax[0] + j];
+  *z = axes[nax[0] + nax[1] + k];
+}
+
+// Occupancy bitmask: bit index of a cell in the 8x8x8-tile layout of dmf_gridbits.hpp (tile << 9 |
+// (x&7)*64 + (y&7)*8 + (z&7)).  A march sample stays in one tile for several samples whatever the
+// ray direction; with x-major bits (one 128-B line = 1024 z-cells of one (x, y) column) a reverse
+// march left the line at nearly every sample: L2 hit rate 0.50 and 43 GB beyond L2 per 128-pose
 // reverseRayTraceFast launch at 512^3.
 __host__ __device__ inline uint32_t occ_bit(const Geom& g, int x, int y, int z) {
-  const uint32_t nty = ((uint32_t)g.n[1] + 7u) >> 3, ntz = ((uint32_t)g.n[2] + 7u) >> 3;
-  const uint32_t t = (((uint32_t)x >> 3) * nty + ((uint32_t)y >> 3)) * ntz + ((uint32_t)z >> 3);
-  return (t << 9) | (((uint32_t)x & 7u) << 6) | (((uint32_t)y & 7u) << 3) | ((uint32_t)z & 7u);
+  return occ_index(tiles8(g.n[1]), tiles8(g.n[2]), x, y, z);
 }
 // 32-bit words of the tiled bitmask (bit indices must fit 32 bits: checked at construction)
 inline uint64_t occ_words(const int n[3]) {
-  return (uint64_t)((n[0] + 7) >> 3) * (uint64_t)((n[1] + 7) >> 3) * (uint64_t)((n[2] + 7) >> 3) * 16u;
+  return (uint64_t)tiles8(n[0]) * (uint64_t)tiles8(n[1]) * (uint64_t)tiles8(n[2]) * 16u;
 }
 
 __device__ inline bool occ_test(const uint32_t* occ, uint32_t bit) {

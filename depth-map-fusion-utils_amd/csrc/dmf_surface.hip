@@ -3,9 +3,9 @@
 // (L <= free_threshold) face neighbour, in ascending x-major cell index (= ascending getHashId),
 // each with its hash, voxel centre and a normal from the face neighbours' log-odds.  An ordered,
 // exact stream compaction in which almost every cell is rejected:
-//  k_sf_mask    — one streaming pass over the grid (k_rc_mask's load pattern, dmf_raycast.hip): the
-//                 solid and the free 1-bit-per-cell masks in the occupancy bitmask's 8x8x8-tile
-//                 layout (occ_bit, dmf_internal.hpp), and the number of solid cells;
+//  k_sf_mask    — one streaming pass over the grid (the tile mask pass of dmf_gridbits.hpp, shared
+//                 with dmf_raycast.hip): the solid and the free 1-bit-per-cell masks in the
+//                 occupancy bitmask's 8x8x8-tile layout, and the number of solid cells;
 //  k_sf_surface — bit level: surface = solid & (free shifted along -x, +x, -y, +y, -z, +z), the
 //                 shifts carried across words and tiles; the surface mask, and the number of
 //                 surface cells of every (x, y) row of the grid (the unit of the output order);
@@ -19,73 +19,24 @@
 
 namespace dmf {
 
-struct SfTiles {
-  uint32_t ntx, nty, ntz, ntiles;  // 8x8x8-cell tiles per axis and in all (x-major, as occ_bit)
-};
-static SfTiles sf_tiles(const Geom& g) {
-  const uint32_t ntx = ((uint32_t)g.n[0] + 7u) >> 3, nty = ((uint32_t)g.n[1] + 7u) >> 3, ntz = ((uint32_t)g.n[2] + 7u) >> 3;
-  return SfTiles{ntx, nty, ntz, ntx * nty * ntz};
-}
-
-// One workgroup per 32 consecutive tiles = 512 words of each mask.  Thread (tile j = i & 31, word
-// w = i >> 5) reads the word's 4 y-rows of 8 z-cells (16 B each): a wave's loads are 2 x 4 rows of
-// up to 512 contiguous bytes.  The words go through LDS so that the workgroup's 2 x 2 KiB are
-// stored in order.  Cells past the grid (partial tiles) are neither solid nor free.
-constexpr int kSfMaskThreads = 512;
-__global__ __launch_bounds__(kSfMaskThreads) void k_sf_mask(Geom g, SfTiles tl, const int16_t* __restrict__ L,
-                                                            int occ_thr, int free_thr, uint32_t* __restrict__ solid,
-                                                            uint32_t* __restrict__ free_,
-                                                            unsigned long long* __restrict__ nsolid) {
-  __shared__ uint32_t ss[kSfMaskThreads];
-  __shared__ uint32_t sf[kSfMaskThreads];
+// The mask pass (tile_mask_pass, dmf_gridbits.hpp) with two masks, solid and free, and the number
+// of solid cells.  Cells past the grid (partial tiles) are neither solid nor free.
+__global__ __launch_bounds__(kMaskThreads) void k_sf_mask(Geom g, GridTiles tl, const int16_t* __restrict__ L,
+                                                          int occ_thr, int free_thr, uint32_t* __restrict__ solid,
+                                                          uint32_t* __restrict__ free_,
+                                                          unsigned long long* __restrict__ nsolid) {
   __shared__ uint32_t scount;
-  const int i = threadIdx.x, j = i & 31, w = i >> 5;
+  const int i = threadIdx.x;
   if (i == 0) scount = 0;
-  const uint32_t t = blockIdx.x * 32u + (uint32_t)j;
-  uint32_t ws = 0, wf = 0;
-  if (t < tl.ntiles) {
-    const uint32_t tz = t % tl.ntz, r = t / tl.ntz;
-    const int x = (int)(r / tl.nty) * 8 + (w >> 1), y0 = (int)(r % tl.nty) * 8 + (w & 1) * 4, z0 = (int)tz * 8;
-    if (x < g.n[0]) {
-#pragma unroll
-      for (int dy = 0; dy < 4; ++dy) {
-        const int y = y0 + dy;
-        if (y < g.n[1]) {
-          const int16_t* row = L + (((int64_t)x * g.n[1] + y) * g.n[2] + z0);
-          uint32_t bs = 0, bf = 0;
-          if (z0 + 8 <= g.n[2] && ((uintptr_t)row & 15) == 0) {
-            const uint4 q = *(const uint4*)row;
-            const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const int lo = (int)(int16_t)(u[k] & 0xffffu), hi = (int)(int16_t)(u[k] >> 16);
-              bs |= (uint32_t)(lo >= occ_thr) << (2 * k) | (uint32_t)(hi >= occ_thr) << (2 * k + 1);
-              bf |= (uint32_t)(lo <= free_thr) << (2 * k) | (uint32_t)(hi <= free_thr) << (2 * k + 1);
-            }
-          } else {
-            for (int k = 0; k < 8 && z0 + k < g.n[2]; ++k) {
-              const int c = (int)row[k];
-              bs |= (uint32_t)(c >= occ_thr) << k;
-              bf |= (uint32_t)(c <= free_thr) << k;
-            }
-          }
-          ws |= bs << (8 * dy);
-          wf |= bf << (8 * dy);
-        }
-      }
-    }
-  }
-  ss[j * 16 + w] = ws;
-  sf[j * 16 + w] = wf;
-  uint32_t c = (uint32_t)__popc(ws);
+  uint32_t* const out[2] = {solid, free_};
+  uint32_t word[2];
+  tile_mask_pass<2>(g, tl, L, out, word, [=](int c, int k, uint32_t (&b)[2]) {
+    b[0] |= (uint32_t)(c >= occ_thr) << k;
+    b[1] |= (uint32_t)(c <= free_thr) << k;
+  });
+  uint32_t c = (uint32_t)__popc(word[0]);
   for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  __syncthreads();
   if ((i & 63) == 0 && c) atomicAdd(&scount, c);
-  const uint32_t o = blockIdx.x * (uint32_t)kSfMaskThreads + (uint32_t)i;
-  if (o < tl.ntiles * 16u) {
-    solid[o] = ss[i];
-    free_[o] = sf[i];
-  }
   __syncthreads();
   if (i == 0 && scount) atomicAdd(nsolid, (unsigned long long)scount);
 }
@@ -98,7 +49,7 @@ constexpr int kSfThreads = 256, kSfChunk = kSfThreads / 16;
 
 // The surface word of (tile t = (tx, ty, tz), word w): the solid bits with a free face neighbour.
 // A neighbour word outside the grid's tiles contributes no bit.
-__device__ inline uint32_t sf_word(const SfTiles& tl, const uint32_t* __restrict__ solid,
+__device__ inline uint32_t sf_word(const GridTiles& tl, const uint32_t* __restrict__ solid,
                                    const uint32_t* __restrict__ free_, uint32_t tx, uint32_t ty, uint32_t tz, uint32_t t,
                                    uint32_t w) {
   const uint32_t s = solid[t * 16u + w];
@@ -129,7 +80,7 @@ __device__ inline uint32_t sf_word(const SfTiles& tl, const uint32_t* __restrict
 
 // One workgroup per tile column: the surface words, and counts[x * ydim + y] for the column's
 // rows inside the grid (every row of the grid is written by exactly one workgroup).
-__global__ __launch_bounds__(kSfThreads) void k_sf_surface(Geom g, SfTiles tl, const uint32_t* __restrict__ solid,
+__global__ __launch_bounds__(kSfThreads) void k_sf_surface(Geom g, GridTiles tl, const uint32_t* __restrict__ solid,
                                                            const uint32_t* __restrict__ free_,
                                                            uint32_t* __restrict__ surf, int32_t* __restrict__ counts) {
   __shared__ uint32_t cnt[64];
@@ -171,7 +122,7 @@ __global__ void k_sf_totals(const int32_t* __restrict__ bases, int64_t nrows,
 // of a word travel as four 16-bit fields (a row has at most 2048 cells): an inclusive scan over
 // the lanes of equal w (stride 16) in the wave, the waves' totals through LDS, the chunks' totals
 // in a register.  bases = the exclusive scan of the row counts.
-__global__ __launch_bounds__(kSfThreads) void k_sf_emit(Geom g, SfTiles tl, const int16_t* __restrict__ L,
+__global__ __launch_bounds__(kSfThreads) void k_sf_emit(Geom g, GridTiles tl, const int16_t* __restrict__ L,
                                                         const uint32_t* __restrict__ surf,
                                                         const int32_t* __restrict__ bases, int64_t cap,
                                                         uint64_t* __restrict__ hash, float* __restrict__ xyz,
@@ -232,12 +183,11 @@ __global__ __launch_bounds__(kSfThreads) void k_sf_emit(Geom g, SfTiles tl, cons
       const int gz = (z > 0 ? (int)L[c - 1] : 0) - (z + 1 < g.n[2] ? (int)L[c + 1] : 0);
       if (hash) hash[rank] = hash_id(x, y, z);
       if (xyz) {
-        // the voxel centre from the cell index as reverseRayTraceFast and k_rc_cast form it
-        const float fx = (float)((double)x * g.dl[0] + g.mn[0]), fy = (float)((double)y * g.dl[1] + g.mn[1]),
-                    fz = (float)((double)z * g.dl[2] + g.mn[2]);
-        xyz[3 * rank] = (float)((double)fx + g.hdl[0]);
-        xyz[3 * rank + 1] = (float)((double)fy + g.hdl[1]);
-        xyz[3 * rank + 2] = (float)((double)fz + g.hdl[2]);
+        float cen[3];
+        cell_centre(g, x, y, z, cen);
+        xyz[3 * rank] = cen[0];
+        xyz[3 * rank + 1] = cen[1];
+        xyz[3 * rank + 2] = cen[2];
       }
       if (nrm) {
         float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
@@ -260,18 +210,13 @@ static int check_surface_args(const dmf_volume* v, const void* logodds, int64_t 
   if (cap < 0) return fail(DMF_ERR_INVALID, "negative capacity %lld", (long long)cap);
   return DMF_OK;
 }
-static int check_surface_volume(const dmf_volume* v) {
-  DMF_TRY(require_constructed(v));
-  if (v->xdim > 2048 || v->ydim > 2048 || v->zdim > 2048)
-    return fail(DMF_ERR_RANGE, "surface extraction is limited to 2048 cells per axis");
-  return DMF_OK;
-}
+static const char kSfGridLimit[] = "surface extraction is limited to 2048 cells per axis";
 
 // Masks, row counts and their scan (left in the volume's scratch for surface_emit);
 // d_count[2] = {surface cells, solid cells}.
 static int surface_count(dmf_volume* v, const int16_t* d_logodds, int32_t occ, int32_t free_thr, uint64_t* d_count) {
   const Geom g = v->geom();
-  const SfTiles tl = sf_tiles(g);
+  const GridTiles tl = grid_tiles(g.n);
   const size_t words = 16 * (size_t)tl.ntiles;
   const int64_t nrows = (int64_t)g.n[0] * g.n[1];
   void *solid, *free_, *surf, *counts, *bases, *tot;
@@ -283,7 +228,7 @@ static int surface_count(dmf_volume* v, const int16_t* d_logodds, int32_t occ, i
   DMF_TRY(scratch(v, kScSfTotals, sizeof(unsigned long long), &tot));
   DMF_HIP(hipMemsetAsync(tot, 0, sizeof(unsigned long long), v->stream));
   DMF_HIP(hipMemsetAsync((int32_t*)counts + nrows, 0, sizeof(int32_t), v->stream));
-  hipLaunchKernelGGL(k_sf_mask, dim3((tl.ntiles + 31u) / 32u), dim3(kSfMaskThreads), 0, v->stream, g, tl, d_logodds,
+  hipLaunchKernelGGL(k_sf_mask, dim3((tl.ntiles + 31u) / 32u), dim3(kMaskThreads), 0, v->stream, g, tl, d_logodds,
                      occ, free_thr, (uint32_t*)solid, (uint32_t*)free_, (unsigned long long*)tot);
   DMF_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sf_surface, dim3(tl.ntx * tl.nty), dim3(kSfThreads), 0, v->stream, g, tl,
@@ -301,7 +246,7 @@ static int surface_emit(dmf_volume* v, const int16_t* d_logodds, uint64_t* d_has
                         int64_t cap) {
   if (cap <= 0 || (!d_hash && !d_xyz && !d_nrm)) return DMF_OK;
   const Geom g = v->geom();
-  const SfTiles tl = sf_tiles(g);
+  const GridTiles tl = grid_tiles(g.n);
   void *surf, *bases;
   DMF_TRY(scratch(v, kScSfSurf, 0, &surf));
   DMF_TRY(scratch(v, kScSfBases, 0, &bases));
@@ -315,9 +260,8 @@ static int surface_emit(dmf_volume* v, const int16_t* d_logodds, uint64_t* d_has
 static int surface_count_host(dmf_volume* v, const int16_t* logodds, int32_t occ, int32_t free_thr, void** d_grid,
                               uint64_t cnt[2]) {
   void* dc;
-  DMF_TRY(scratch(v, kScOut2, sizeof(int16_t) * v->ncell, d_grid));
+  DMF_TRY(upload_grid(v, logodds, d_grid));
   DMF_TRY(scratch(v, kScOut3, sizeof(uint64_t) * 2, &dc));
-  DMF_HIP(hipMemcpyAsync(*d_grid, logodds, sizeof(int16_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
   DMF_TRY(surface_count(v, (const int16_t*)*d_grid, occ, free_thr, (uint64_t*)dc));
   DMF_HIP(hipMemcpyAsync(cnt, dc, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost, v->stream));
   DMF_HIP(hipStreamSynchronize(v->stream));
@@ -336,7 +280,7 @@ int dmf_grid_surface_device(dmf_volume* v, const int16_t* d_logodds, int32_t occ
   DMF_TRY(check_surface_args(v, d_logodds, cap));
   if (!d_count) return fail(DMF_ERR_INVALID, "null d_count");
   if (!d_hash && !d_xyz && !d_normals) return fail(DMF_ERR_INVALID, "every output is null");
-  DMF_TRY(check_surface_volume(v));
+  DMF_TRY(require_grid_2048(v, kSfGridLimit));
   DMF_TRY(surface_count(v, d_logodds, occ_threshold, free_threshold, d_count));
   return surface_emit(v, d_logodds, d_hash, d_xyz, d_normals, cap);
   DMF_API_END
@@ -346,7 +290,7 @@ int dmf_grid_surface(dmf_volume* v, const int16_t* logodds, int32_t occ_threshol
                      uint64_t* hash, float* xyz, float* normals, int64_t cap, int64_t* n, int64_t* n_solid) {
   DMF_API_BEGIN
   DMF_TRY(check_surface_args(v, logodds, cap));
-  DMF_TRY(check_surface_volume(v));
+  DMF_TRY(require_grid_2048(v, kSfGridLimit));
   void* dl;
   uint64_t cnt[2] = {0, 0};
   DMF_TRY(surface_count_host(v, logodds, occ_threshold, free_threshold, &dl, cnt));
@@ -376,7 +320,7 @@ int dmf_volume_integrate_surface(dmf_volume* v, const int16_t* logodds, int32_t 
                                  int64_t* n) {
   DMF_API_BEGIN
   DMF_TRY(check_surface_args(v, logodds, 0));
-  DMF_TRY(check_surface_volume(v));
+  DMF_TRY(require_grid_2048(v, kSfGridLimit));
   void* dl;
   uint64_t cnt[2] = {0, 0};
   DMF_TRY(surface_count_host(v, logodds, occ_threshold, free_threshold, &dl, cnt));

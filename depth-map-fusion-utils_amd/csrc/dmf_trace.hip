@@ -146,22 +146,12 @@ __global__ __launch_bounds__(256) void k_reverse(Geom g, DevVol vd, CamP cam, co
       slot = e;
       const uint64_t h = vd.hash[e];
       const int xid = (int)(h >> 40), yid = (int)((h >> 20) & 0xFFFFF), zid = (int)(h & 0xFFFFF);
-      // :151-153 x = xid*xdelta_ + xmin_ (float); :157 centroid = x + xdelta_/2.0 (float)
-      const float x = (float)((double)xid * g.dl[0] + g.mn[0]);
-      const float y = (float)((double)yid * g.dl[1] + g.mn[1]);
-      const float z = (float)((double)zid * g.dl[2] + g.mn[2]);
-      cen[0] = (float)((double)x + g.hdl[0]);
-      cen[1] = (float)((double)y + g.hdl[1]);
-      cen[2] = (float)((double)z + g.hdl[2]);
+      cell_centre(g, xid, yid, zid, cen);
     } else {
-      const uint32_t en = el.list[e];
-      const uint32_t nyz = (uint32_t)el.nax[1] * (uint32_t)el.nax[2];
-      const uint32_t i = en / nyz, j = (en / el.nax[2]) % el.nax[1], k = en % el.nax[2];
-      const float x = el.axes[i], y = el.axes[el.nax[0] + j], z = el.axes[el.nax[0] + el.nax[1] + k];
+      float x, y, z;
+      enum_xyz(el.axes, el.nax, el.list[e], &x, &y, &z);
       slot = vd.slot_of[lin_index(g, bin_axis(g, 0, x), bin_axis(g, 1, y), bin_axis(g, 2, z))];
-      cen[0] = (float)((double)x + g.hdl[0]);
-      cen[1] = (float)((double)y + g.hdl[1]);
-      cen[2] = (float)((double)z + g.hdl[2]);
+      centre_of_corner(g, x, y, z, cen);
     }
     const PoseX& T = poses[p];
     float t[3];
@@ -372,21 +362,12 @@ __device__ inline bool rev_wave(const Geom& g, const DevVol& vd, const CamP& cam
             slot = kOrder ? (int32_t)order[e] : (int32_t)e;
             const uint64_t h = vd.hash[slot];
             const int xid = (int)(h >> 40), yid = (int)((h >> 20) & 0xFFFFF), zid = (int)(h & 0xFFFFF);
-            const float x = (float)((double)xid * g.dl[0] + g.mn[0]);
-            const float y = (float)((double)yid * g.dl[1] + g.mn[1]);
-            const float z = (float)((double)zid * g.dl[2] + g.mn[2]);
-            cen[0] = (float)((double)x + g.hdl[0]);
-            cen[1] = (float)((double)y + g.hdl[1]);
-            cen[2] = (float)((double)z + g.hdl[2]);
+            cell_centre(g, xid, yid, zid, cen);
           } else {
-            const uint32_t en = el.list[e];
-            const uint32_t nyz = (uint32_t)el.nax[1] * (uint32_t)el.nax[2];
-            const uint32_t i = en / nyz, j = (en / el.nax[2]) % el.nax[1], k = en % el.nax[2];
-            const float x = el.axes[i], y = el.axes[el.nax[0] + j], z = el.axes[el.nax[0] + el.nax[1] + k];
+            float x, y, z;
+            enum_xyz(el.axes, el.nax, el.list[e], &x, &y, &z);
             slot = vd.slot_of[lin_index(g, bin_axis(g, 0, x), bin_axis(g, 1, y), bin_axis(g, 2, z))];
-            cen[0] = (float)((double)x + g.hdl[0]);
-            cen[1] = (float)((double)y + g.hdl[1]);
-            cen[2] = (float)((double)z + g.hdl[2]);
+            centre_of_corner(g, x, y, z, cen);
           }
           float t[3];
           xform(T.i, cen[0], cen[1], cen[2], t);
@@ -1424,8 +1405,8 @@ __global__ void k_forward_post(Geom g, DevVol vd, CamP cam, const PoseX* __restr
   float pc[3], w[3];
   project(cam, r, c, zd, pc);
   xform(pose->f, pc[0], pc[1], pc[2], w);
-  const float cen[3] = {(float)((double)w[0] + g.hdl[0]), (float)((double)w[1] + g.hdl[1]),
-                        (float)((double)w[2] + g.hdl[2])};
+  float cen[3];
+  centre_of_corner(g, w[0], w[1], w[2], cen);
   const float d[3] = {pose->f[3] - cen[0], pose->f[7] - cen[1], pose->f[11] - cen[2]};
   float v[3];
   normalized(d, v);
@@ -1575,12 +1556,10 @@ __global__ void k_zbuffer(Geom g, DevVol vd, CamP cam, const PoseX* __restrict__
                           int pass, int* __restrict__ zbuf, unsigned long long* __restrict__ hazards) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
-  const uint32_t en = el.list[e];
-  const uint32_t nyz = (uint32_t)el.nax[1] * (uint32_t)el.nax[2];
-  const uint32_t i = en / nyz, j = (en / el.nax[2]) % el.nax[1], k = en % el.nax[2];
-  const float x = el.axes[i], y = el.axes[el.nax[0] + j], z = el.axes[el.nax[0] + el.nax[1] + k];
-  float t[3];
-  xform(pose->i, (float)((double)x + g.hdl[0]), (float)((double)y + g.hdl[1]), (float)((double)z + g.hdl[2]), t);
+  float x, y, z, cen[3], t[3];
+  enum_xyz(el.axes, el.nax, el.list[e], &x, &y, &z);
+  centre_of_corner(g, x, y, z, cen);
+  xform(pose->i, cen[0], cen[1], cen[2], t);
   int r, c;
   if (!deproject_valid(cam, t[0], t[1], t[2], r, c)) return;
   const int d = to_int_x86((double)roundf(t[2] * 1000.0f));
