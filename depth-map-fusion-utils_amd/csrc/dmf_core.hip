@@ -787,8 +787,10 @@ int dmf_volume_destroy(dmf_volume* v) {
   (void)hipDeviceSynchronize();
   free_state(v);
   if (v->switch_ev) (void)hipEventDestroy(v->switch_ev);
-  for (hipEvent_t e : {v->st_in, v->st_done[0], v->st_done[1], v->st_free[0], v->st_free[1], v->st_b[0], v->st_b[1], v->st_a[0], v->st_a[1]})
-    if (e) (void)hipEventDestroy(e);
+  if (v->st_in) (void)hipEventDestroy(v->st_in);
+  for (const dmf_volume::StageSlot& s : v->slots)
+    for (hipEvent_t e : {s.done, s.free, s.a, s.b})
+      if (e) (void)hipEventDestroy(e);
   if (v->stage) (void)hipStreamDestroy(v->stage);
   delete v;
   return DMF_OK;

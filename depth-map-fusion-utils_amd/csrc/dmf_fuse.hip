@@ -1752,10 +1752,12 @@ static bool use_bricks(const dmf_volume* v, const Geom& g) {
 // 1 % faster than 4 at 512^3 and at config 2, the others slower); with 8-slab blocks a wave
 // refills at >= 16 idle lanes (sweep 16/20/24/32, picks over 16/32/64 regions: serial -1 %,
 // config 2 -0.5 %, pipelined within the box's drift)
-constexpr int kBkUnroll = 8;
-constexpr int kBkRefill = 16, kBkSpread = 32;  // refill threshold / pick spread of phase F
+// Each fusion kernel's template arguments beside the name dmf_fuse_kernel_name reports for it
+constexpr int kBkRefill = 16, kBkSpread = 32, kBkUnroll = 8;  // refill threshold / pick spread / slabs per block
 constexpr const char* kNameSlab = "dmf::k_bk_fuse_s<16, 32, 8>";
+constexpr int kCellRefill = 16, kCellOrder = 8, kCellUnroll = 8;  // the per-cell walk's
 constexpr const char* kNameCell = "dmf::k_bk_fuse<16, 8, 8>";
+constexpr int kLdsS = 12, kLdsBox = 1280;
 constexpr const char* kNameLds = "dmf::k_fuse_l<12, 1280>";
 
 static int cu_count(int device) {
@@ -1776,10 +1778,12 @@ static int cu_count(int device) {
 // into batches by the pairs they really make against the pair capacity (the rest of the
 // slot's budget, at most the geometric bound of the super-batch); the host launches jmax =
 // the batches the geometric bound rays x (1 + brick boundaries) would need, and the launches
-// past the device's batch count exit at once.  Budget (dmf_fuse_reserve): 55 % of the
-// device's HBM by default (~158 GB of MI355X's 288 GB), all of it for the one slot of serial
+// past the device's batch count exit at once.  Budget (dmf_fuse_reserve): 45 % of the
+// device's HBM by default (~130 GB of MI355X's 288 GB), all of it for the one slot of serial
 // calls, half of it for each of the two staging slots of pipelined calls: the 1024-pose
-// 512^3 anchor and the 256-pose 1024^3 shard each run as one batch either way.
+// 512^3 anchor runs as one batch per call either way, the 256-pose 1024^3 shard as two
+// batches per pipelined call, in the time of one batch at 55 % (dmf_volume_create, DESIGN.md
+// §5.8, §5.10).
 
 struct BkPlan {
   BkGeom bg;
@@ -1806,6 +1810,43 @@ struct BkPlan {
 // 64-ray packets per frame of a ray source: 8x8 pixel packets of a camera, ceil(N / 64) of a scan
 static int64_t cam_packets(const CamP& cp) { return (int64_t)((cp.W + 7) / 8) * ((cp.H + 7) / 8); }
 static int64_t scan_packets(int64_t N) { return (N + 63) / 64; }
+
+// The bytes of each buffer of a staging slot (BkBuf, dmf_host.hpp), stated once; `counted`: the
+// part of them the budget counts (bk_plan: PS, pair_cap, slot_bytes).  It does not count the
+// spare pair record that pass B's store guard writes to, the batch table's four alignment words,
+// the overflow list, and a staged call's pose table and statistics: counting them would move
+// PS and pair_cap at the margins.
+static uint64_t bk_buf_bytes(const BkPlan& pl, int buf, bool counted = false) {
+  const uint64_t PS = (uint64_t)pl.PS, wgs = (uint64_t)pl.wg_pose * PS, spare = counted ? 0 : 1;
+  if (counted && buf >= kBufOvl) return 0;
+  switch (buf) {
+    case kBufRays: return PS * (uint64_t)pl.ppose * 64 * (sizeof(ulonglong2) + sizeof(uint64_t));
+    case kBufPairsA: return sizeof(uint4) * (pl.pair_cap + spare);
+    case kBufPairsB: return (pl.rec_bytes - sizeof(uint4)) * (pl.pair_cap + spare);
+    // cnt | off | part_pref (nbricks + 1) | order (uint2 per part)
+    case kBufBricks: return sizeof(uint32_t) * (3 * (uint64_t)pl.bg.nbricks + 6 + 2 * pl.max_parts());
+    case kBufCtl: return sizeof(unsigned long long) * 4;
+    case kBufWgBase: return wgs * pl.hist_bytes;
+    // touched-brick list per workgroup: count + one word per touched brick (uint16 id | uint16
+    // pair count: pass B's layout check; ADVICE r5 -- 1.5 words per brick before)
+    case kBufWgList: return wgs * sizeof(uint32_t) * (uint64_t)pl.wgl_stride;
+    case kBufPoseCnt:
+    case kBufPoseBase: return PS * pl.hist_bytes;
+    case kBufBatch: return sizeof(unsigned long long) * PS + sizeof(uint32_t) * (PS + 4 * spare);
+    case kBufOvl: return sizeof(uint32_t) * (1 + wgs);
+    case kBufStPoses: return sizeof(PoseX) * PS;
+    case kBufStStats: return sizeof(unsigned long long) * kStatSlots * kStatWidth;
+  }
+  return 0;
+}
+// What the budget counts of a slot with PS poses (linear in PS: the bytes per pose are those of
+// one pose less those of none)
+static uint64_t bk_counted_bytes(BkPlan pl, int64_t PS) {
+  pl.PS = PS;
+  uint64_t n = 0;
+  for (int k = 0; k < kBkBufCount; ++k) n += bk_buf_bytes(pl, k, true);
+  return n;
+}
 
 // `ppose` = packets per pose (cam_packets) or per scan (scan_packets); P = poses or scans
 static int bk_plan(const dmf_volume* v, int64_t ppose, const Geom& g, int P, BkPlan& pl) {
@@ -1841,13 +1882,9 @@ static int bk_plan(const dmf_volume* v, int64_t ppose, const Geom& g, int P, BkP
     pl.part_max = (uint32_t)std::max<int64_t>(1024, std::min<int64_t>(kn[DMF_KNOB_PART_MAX], kBkPartMax));
   pl.wg_pose = (int)((pl.ppose + pl.span - 1) / pl.span);
   pl.hist_bytes = sizeof(uint32_t) * (size_t)pl.bg.nbricks;
-  // per pose: ray records, per-workgroup brick bases, pose counts and bases, pose pairs + batch table
-  // touched-brick list per workgroup: count + one word per touched brick (uint16 id | uint16
-  // pair count: pass B's layout check; ADVICE r5 -- 1.5 words per brick before)
   pl.wgl_stride = 1 + pl.bg.nbricks;
-  pl.per_pose_bytes = (uint64_t)rays_pose * (sizeof(ulonglong2) + sizeof(uint64_t)) + (uint64_t)pl.wg_pose * pl.hist_bytes +
-                      (uint64_t)pl.wg_pose * sizeof(uint32_t) * (uint64_t)pl.wgl_stride + 2 * (uint64_t)pl.hist_bytes +
-                      sizeof(unsigned long long) + sizeof(uint32_t);
+  // per pose: ray records, per-workgroup brick bases and lists, pose counts and bases, pose pairs + batch table
+  pl.per_pose_bytes = bk_counted_bytes(pl, 1) - bk_counted_bytes(pl, 0);
   // pipelined calls: two staging slots, each with its own pair records, share the budget
   pl.slots = v->pipelined ? 2 : 1;
   const uint64_t budget = v->bk_budget / (uint64_t)pl.slots;
@@ -1871,9 +1908,7 @@ static int bk_plan(const dmf_volume* v, int64_t ppose, const Geom& g, int P, BkP
     const int k = ts > 0 ? (int)std::min<int64_t>(ts, 8) : 2;  // entries split: k per CU
     pl.split_cu = std::min(512, cu_count(v->device)) | (k << 16);
   }
-  pl.slot_bytes = pl.pair_cap * pl.rec_bytes + (uint64_t)pl.PS * pl.per_pose_bytes +
-                  sizeof(uint32_t) * (3 * (uint64_t)pl.bg.nbricks + 6 + 2 * pl.max_parts()) +
-                  sizeof(unsigned long long) * 4;
+  pl.slot_bytes = bk_counted_bytes(pl, pl.PS);
   return DMF_OK;
 }
 
@@ -1915,41 +1950,24 @@ struct BkBufs {
 // pipelined fusion (serial calls use slot 0).
 static int bk_scratch(dmf_volume* v, const BkPlan& pl, BkBufs& b, int slot) {
   const size_t PS = (size_t)pl.PS, nb = (size_t)pl.bg.nbricks;
-  void *rays, *bricks, *ctl, *wgb, *wgl, *pra, *prb, *pcnt, *pbase, *batch;
-  const size_t nrays = (size_t)(pl.PS * pl.ppose * 64);  // ray records, then the crossing paths
-  DMF_TRY(scratch(v, slot ? kScBkRays1 : kScBkRays, (sizeof(ulonglong2) + sizeof(uint64_t)) * nrays, &rays));
-  // cnt | off | part_pref (nbricks + 1) | order (uint2 per part)
-  DMF_TRY(scratch(v, slot ? kScBkBricks1 : kScBkBricks, sizeof(uint32_t) * (3 * nb + 6 + 2 * pl.max_parts()), &bricks));
-  DMF_TRY(scratch(v, slot ? kScBkCtl1 : kScBkCtl, sizeof(unsigned long long) * 4, &ctl));
-  DMF_TRY(scratch(v, slot ? kScBkWgBase1 : kScBkWgBase, pl.hist_bytes * (size_t)pl.wg_pose * PS, &wgb));
-  DMF_TRY(scratch(v, slot ? kScBkWgList1 : kScBkWgList,
-                  sizeof(uint32_t) * (size_t)pl.wgl_stride * (size_t)pl.wg_pose * PS, &wgl));
-  // pair records: pair_cap, plus the spare record pass B's store guard writes to
-  DMF_TRY(scratch(v, slot ? kScBkPairs1 : kScBkPairs, sizeof(uint4) * ((size_t)pl.pair_cap + 1), &pra));
-  DMF_TRY(scratch(v, slot ? kScBkPairsB1 : kScBkPairsB, (pl.rec_bytes - sizeof(uint4)) * ((size_t)pl.pair_cap + 1),
-                  &prb));
-  DMF_TRY(scratch(v, slot ? kScBkPoseCnt1 : kScBkPoseCnt, pl.hist_bytes * PS, &pcnt));
-  DMF_TRY(scratch(v, slot ? kScBkPoseBase1 : kScBkPoseBase, pl.hist_bytes * PS, &pbase));
-  DMF_TRY(scratch(v, slot ? kScBkBatch1 : kScBkBatch, sizeof(unsigned long long) * PS + sizeof(uint32_t) * (PS + 4),
-                  &batch));
-  void* ovl;
-  DMF_TRY(scratch(v, slot ? kScBkOvf1 : kScBkOvf, sizeof(uint32_t) * (1 + (size_t)pl.wg_pose * PS), &ovl));
-  b.ovl = (uint32_t*)ovl;
-  b.rays = (ulonglong2*)rays;
-  b.paths = (uint64_t*)(b.rays + nrays);
-  b.cnt = (uint32_t*)bricks;
+  void* p[kBkPipeBufs];
+  for (int k = 0; k < kBkPipeBufs; ++k) DMF_TRY(scratch(v, bk_key(k, slot), bk_buf_bytes(pl, k), &p[k]));
+  b.rays = (ulonglong2*)p[kBufRays];
+  b.paths = (uint64_t*)(b.rays + PS * (size_t)pl.ppose * 64);
+  b.pra = (uint4*)p[kBufPairsA];
+  b.prb = p[kBufPairsB];
+  b.cnt = (uint32_t*)p[kBufBricks];
   b.off = b.cnt + nb;
   b.part_pref = b.off + nb;  // nbricks + 1
   b.order = (uint2*)(b.part_pref + nb + 4 + (nb & 1));  // 8-B aligned
-  b.wgb = (uint32_t*)wgb;
-  b.wgl = (uint32_t*)wgl;
-  b.ctl = (unsigned long long*)ctl;
-  b.pra = (uint4*)pra;
-  b.prb = prb;
-  b.pose_cnt = (uint32_t*)pcnt;
-  b.pose_base = (uint32_t*)pbase;
-  b.pose_pairs = (unsigned long long*)batch;
+  b.ctl = (unsigned long long*)p[kBufCtl];
+  b.wgb = (uint32_t*)p[kBufWgBase];
+  b.wgl = (uint32_t*)p[kBufWgList];
+  b.pose_cnt = (uint32_t*)p[kBufPoseCnt];
+  b.pose_base = (uint32_t*)p[kBufPoseBase];
+  b.pose_pairs = (unsigned long long*)p[kBufBatch];
   b.bt = (uint32_t*)(b.pose_pairs + PS);
+  b.ovl = (uint32_t*)p[kBufOvl];
   return DMF_OK;
 }
 
@@ -1957,13 +1975,9 @@ static int bk_scratch(dmf_volume* v, const BkPlan& pl, BkBufs& b, int slot) {
 // it: a volume switching between serial and pipelined calls re-plans its slots against the
 // budget (one slot of the whole budget, or two of half).
 static int bk_release(dmf_volume* v) {
-  static const int kSlots[] = {kScBkRays, kScBkPairs, kScBkPairsB, kScBkBricks, kScBkWgBase, kScBkCtl, kScBkPoseCnt,
-                               kScBkPoseBase, kScBkBatch, kScBkWgList, kScBkRays1, kScBkWgBase1, kScBkWgList1,
-                               kScBkPoseCnt1, kScBkBatch1, kScBkBricks1, kScBkCtl1, kScBkPairs1, kScBkPairsB1,
-                               kScBkPoseBase1, kScBkOvf, kScBkOvf1};
   if (v->stream) DMF_HIP(hipStreamSynchronize(v->stream));
   if (v->stage) DMF_HIP(hipStreamSynchronize(v->stage));
-  for (int k : kSlots) {
+  for (int k = kScBkFirst; k < kScBkEnd; ++k) {
     if (k < (int)v->scratch.size() && v->scratch[k].first) {
       DMF_HIP(hipFree(v->scratch[k].first));
       v->scratch[k] = {nullptr, 0};
@@ -1980,28 +1994,22 @@ static int bk_release(dmf_volume* v) {
 // when the queue is empty).
 // Pipelined (staged): the pose table and pass A of each super-batch run on
 // the volume's staging stream into staging slot s (alternating), after the caller's input
-// stream and after the slot's previous reader (event st_free[s]), beside the previous call's
+// stream and after the slot's previous reader (event slots[s].free), beside the previous call's
 // phase F; the batch cut, the brick layout, pass B and phase F run on the volume's stream
 // after pass A's event; the input stream waits for pass A (the inputs stay ordered before the
 // caller's next writes).  Pass A's statistics go to the slot's own striped buffer, summed into
 // d_user on the staging stream.  Serial calls use slot 0 on the volume's stream; once the staging stream exists
-// they record st_free[0] too, so that a later pipelined call on slot 0 waits for them.
+// they record slots[0].free too, so that a later pipelined call on slot 0 waits for them.
 static int stage_init(dmf_volume* v) {
   if (v->stage) return DMF_OK;
   DMF_HIP(hipStreamCreateWithFlags(&v->stage, hipStreamNonBlocking));
   DMF_HIP(hipEventCreateWithFlags(&v->st_in, hipEventDisableTiming));
-  for (int k = 0; k < 2; ++k) {
-    DMF_HIP(hipEventCreateWithFlags(&v->st_done[k], hipEventDisableTiming));
-    DMF_HIP(hipEventCreateWithFlags(&v->st_free[k], hipEventDisableTiming));
-    DMF_HIP(hipEventCreateWithFlags(&v->st_b[k], hipEventDisableTiming));
-    DMF_HIP(hipEventCreateWithFlags(&v->st_a[k], hipEventDisableTiming));
-    v->st_b_set[k] = false;
-    v->st_free_set[k] = false;
-  }
+  for (dmf_volume::StageSlot& s : v->slots)  // (free_set and b_set are still false)
+    for (hipEvent_t* e : {&s.done, &s.free, &s.b, &s.a}) DMF_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
   // work already enqueued on the volume's stream (a serial call's slot 0 readers) precedes
   // the first staged use of slot 0
-  DMF_HIP(hipEventRecord(v->st_free[0], v->stream));
-  v->st_free_set[0] = true;
+  DMF_HIP(hipEventRecord(v->slots[0].free, v->stream));
+  v->slots[0].free_set = true;
   return DMF_OK;
 }
 
@@ -2014,196 +2022,6 @@ static int fault_words(dmf_volume* v) {
   v->d_fault = (uint32_t*)p;
   DMF_HIP(hipMemsetAsync(p, 0, 2 * sizeof(uint32_t), v->stream));
   DMF_HIP(hipStreamSynchronize(v->stream));
-  return DMF_OK;
-}
-
-// The host side of a ray source: the frames of one call, and the device source of the
-// super-batch of frames [s0, s0 + ps) as pass A reads it on stream sa.
-struct DepthFeed {
-  using Src = DepthSrc;
-  CamP cp;
-  const uint16_t* d_depth;
-  const PoseX* tab;       // the call's pose table (serial calls)
-  const float* d_poses;   // the caller's poses (staged calls build the slot's table from them)
-  int dmin, dmax;
-  int64_t packets() const { return cam_packets(cp); }
-  int source(dmf_volume* v, int64_t s0, int64_t ps, int64_t PS, bool staged, int slot, hipStream_t sa, Src& out) const {
-    const PoseX* tab_a = tab + s0;
-    if (staged) {
-      void* t;
-      DMF_TRY(scratch(v, slot ? kScStPoses1 : kScStPoses0, sizeof(PoseX) * (size_t)PS, &t));
-      DMF_TRY(pose_table_into(d_poses + (size_t)s0 * 12, (int)ps, (PoseX*)t, sa));
-      tab_a = (const PoseX*)t;
-    }
-    out = Src{cp, d_depth + (size_t)s0 * cp.H * cp.W, tab_a, dmin, dmax, (cp.W + 7) / 8};
-    return DMF_OK;
-  }
-};
-// Points: the scans' origins take the pose table's place, read as the caller wrote them (a
-// staged pass A follows the input stream as it does for depth frames).
-struct PointFeed {
-  using Src = PointSrc;
-  const float* d_xyz;
-  const float* d_origins;
-  int64_t N;
-  int64_t packets() const { return scan_packets(N); }
-  int source(dmf_volume*, int64_t s0, int64_t, int64_t, bool, int, hipStream_t, Src& out) const {
-    out = Src{d_xyz + (size_t)s0 * (size_t)N * 3, d_origins + (size_t)s0 * 3, N};
-    return DMF_OK;
-  }
-};
-
-template <class Feed>
-static int fuse_bricks(dmf_volume* v, const Feed& feed, const Geom& g, int P, int32_t* d_hits, int32_t* d_misses,
-                       unsigned long long* st, uint64_t* d_user, bool staged, bool capturing) {
-  using Src = typename Feed::Src;
-  BkPlan pl;
-  DMF_TRY(bk_plan(v, feed.packets(), g, P, pl));
-  const BkGeom& bg = pl.bg;
-  DMF_TRY(bk_attributes());
-  DMF_TRY(fault_words(v));
-  BkBufs b;
-  if (staged) DMF_TRY(stage_init(v));
-  const bool slab = v->fuse_variant != DMF_FUSE_CELL_WALK;
-  // pass A with 16-bit histogram counts (a workgroup's pairs per brick <= span * 64 rays; the
-  // plan holds span <= 1023)
-  if ((int64_t)pl.span * 64 > 65535) return fail(DMF_ERR_RANGE, "pass A span %d exceeds 16-bit counts", pl.span);
-  const unsigned nf = (unsigned)cu_count(v->device);  // phase F's persistent workgroups: one per CU
-  // pass B and the brick scan, each one launch whatever the variant / grid size
-  auto pass_b = [&](auto kernel, unsigned nwg, hipStream_t s, int64_t j) {
-    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(pl.ab_threads), pl.hist_bytes, s, (int)pl.ppose, pl.wg_pose, pl.span, bg,
-                       (const ulonglong2*)b.rays, (const uint64_t*)b.paths, (const uint32_t*)b.off,
-                       (const uint32_t*)b.pose_base, (const uint32_t*)b.wgb, (const uint32_t*)b.bt, (int)j,
-                       (const uint32_t*)b.wgl, pl.wgl_stride, b.pra, b.prb, b.ctl, v->d_fault,
-                       (int)std::min<int64_t>(v->knob[DMF_KNOB_FAULT_INJECT], 1 << 20), st);
-  };
-  auto scan = [&](auto kernel, hipStream_t s, int64_t j) {
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(1024), 0, s, bg.nbricks, (const uint32_t*)b.cnt, b.off, b.part_pref, b.ctl,
-                       b.order, pl.part_max, (const uint32_t*)b.bt, (int)j, pl.split_cu);
-  };
-  for (int64_t s0 = 0; s0 < P; s0 += pl.PS) {
-    const int64_t ps = std::min<int64_t>(pl.PS, P - s0);
-    const unsigned nwg = (unsigned)(ps * pl.wg_pose);
-    const int slot = staged ? v->st_slot : 0;
-    DMF_TRY(bk_scratch(v, pl, b, slot));
-    // everything but phase F: the staging stream (pipelined) or the volume's stream
-    const hipStream_t sa = staged ? v->stage : v->stream;
-    unsigned long long* st_a = st;
-    if (staged) {
-      v->st_slot ^= 1;
-      DMF_HIP(hipEventRecord(v->st_in, v->in_stream));
-      DMF_HIP(hipStreamWaitEvent(sa, v->st_in, 0));
-      if (v->st_free_set[slot]) DMF_HIP(hipStreamWaitEvent(sa, v->st_free[slot], 0));
-    }
-    Src src;  // (a staged depth call's pose table is built here, on the staging stream)
-    DMF_TRY(feed.source(v, s0, ps, pl.PS, staged, slot, sa, src));
-    if (staged) {
-      if (st) {
-        void* sbuf;
-        DMF_TRY(scratch(v, slot ? kScStStats1 : kScStStats0, sizeof(unsigned long long) * kStatSlots * kStatWidth, &sbuf));
-        DMF_HIP(hipMemsetAsync(sbuf, 0, sizeof(unsigned long long) * kStatSlots * kStatWidth, sa));
-        st_a = (unsigned long long*)sbuf;
-      }
-    }
-    DMF_HIP(hipMemsetAsync(b.pose_cnt, 0, pl.hist_bytes * (size_t)ps, sa));
-    DMF_HIP(hipMemsetAsync(b.pose_pairs, 0, sizeof(unsigned long long) * (size_t)ps, sa));
-    // pass A after the previous super-batch's pass B: it then runs beside that super-batch's
-    // phase F (launched at once, it would run beside pass B instead, and phase F alone); the
-    // pose table and the zeroing above may run beside pass B
-    if (staged && v->st_b_set[slot ^ 1]) DMF_HIP(hipStreamWaitEvent(sa, v->st_b_ev[slot ^ 1], 0));
-    BkRaysArgs<Src> ra{g, src, (int)pl.ppose, pl.wg_pose, pl.span, bg, b.rays, b.paths, b.pose_cnt, b.wgb, b.wgl,
-                       pl.wgl_stride, b.pose_pairs, st_a, b.ovl, 0};
-    if (pl.hash_log > 0) {
-      // hashed histogram (8 KB: beside phase F's box), then the overflowed workgroups (if any)
-      // with the direct table
-      ra.hash_log = pl.hash_log;
-      DMF_HIP(hipMemsetAsync(b.ovl, 0, sizeof(uint32_t), sa));
-      hipLaunchKernelGGL(k_bk_rays_hash<Src>, dim3(nwg), dim3(kBkPassThreads), sizeof(uint32_t) << pl.hash_log, sa, ra);
-      DMF_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_bk_rays_recover<Src>, dim3(nf), dim3(kBkPassThreadsBig),
-                         sizeof(uint32_t) * ((bg.nbricks + 1) / 2), sa, ra);
-    } else {
-      hipLaunchKernelGGL((k_bk_rays<true, Src>), dim3(nwg), dim3(pl.ab_threads),
-                         sizeof(uint32_t) * ((bg.nbricks + 1) / 2), sa, ra);
-    }
-    DMF_LAUNCH_CHECK();
-    if (staged) {
-      // the layout, pass B and phase F on the volume's stream after pass A (event st_a): pass
-      // B follows the previous call's phase F in stream order (it never ran beside it: pass
-      // A's tail outlasts F), and phase F follows pass B with no cross-stream event (13 -> 7
-      // us per call).  Pass A's statistics are then summed here, on the staging stream
-      // (atomic sums: the previous call's are summed on the volume's stream meanwhile), off
-      // the chain to pass B; st_done (after them) orders the input stream, and the volume's
-      // stream after this call's phase F.
-      DMF_HIP(hipEventRecord(v->st_a[slot], sa));
-      DMF_HIP(hipStreamWaitEvent(v->stream, v->st_a[slot], 0));
-      if (st) DMF_TRY(stats_end(v, st_a, d_user, kStatWidth, nullptr, sa));
-      DMF_HIP(hipEventRecord(v->st_done[slot], sa));
-      DMF_HIP(hipStreamWaitEvent(v->in_stream, v->st_done[slot], 0));
-    }
-    // everything after pass A: the volume's stream
-    const hipStream_t sl = v->stream;
-    // small grids: batch cut, brick counts and scan in one launch per batch (k_bk_layout1)
-    const bool layout1 = bg.nbricks <= kBkLayout1Bricks && ps <= kBkLayout1Poses;
-    if (!layout1) {
-      hipLaunchKernelGGL(k_bk_batches, dim3(1), dim3(1024), 0, sl, (int)ps, (const unsigned long long*)b.pose_pairs,
-                         (unsigned long long)pl.pair_cap, pl.max_poses, b.bt);
-      DMF_LAUNCH_CHECK();
-    }
-    v->bk_last_bt = b.bt;
-    const int64_t jm = pl.jmax(ps);
-    for (int64_t j = 0; j < jm; ++j) {
-      // batch j > 0 reuses the slot's pair records and part queue, so it follows batch j-1's
-      // phase F in stream order.  The host launches jmax triples from the one-pose bound;
-      // those past the device's batch count exit at once (1024^3: jmax 7, one batch).
-      const hipStream_t sj = sl;
-      // (the scan zeroes phase F's queue head: no memset of ctl)
-      if (layout1) {
-        hipLaunchKernelGGL(k_bk_layout1, dim3(1), dim3(1024), 0, sj, (int)ps, (const unsigned long long*)b.pose_pairs,
-                           (unsigned long long)pl.pair_cap, pl.max_poses, b.bt, bg.nbricks, (int)j,
-                           (const uint32_t*)b.pose_cnt, b.pose_base, b.cnt, b.off, b.part_pref, b.ctl, b.order,
-                           pl.part_max, pl.split_cu);
-      } else {
-        hipLaunchKernelGGL(k_bk_batch_counts, dim3((unsigned)((bg.nbricks + 255) / 256)), dim3(256), 0, sj,
-                           bg.nbricks, (int)j, (const uint32_t*)b.bt, (const uint32_t*)b.pose_cnt, b.pose_base, b.cnt);
-        DMF_LAUNCH_CHECK();
-        if (bg.nbricks > 4096) scan(k_bk_scan<true>, sj, j);
-        else scan(k_bk_scan<false>, sj, j);
-      }
-      DMF_LAUNCH_CHECK();
-      if (slab) pass_b(k_bk_pairs<true>, nwg, sj, j);
-      else pass_b(k_bk_pairs<false>, nwg, sj, j);
-      DMF_LAUNCH_CHECK();
-      // the call's phase F begins (not while capturing: the record would become a graph node
-      // and the caller's event would never be re-recorded by the graph's launches)
-      const bool fev = v->f_event && !capturing && s0 == 0 && j == 0;
-      if (fev) DMF_HIP(hipEventRecord(v->f_event, v->stream));
-      if (staged && j == 0) {
-        // pass B done: the next super-batch's pass A waits for it (the caller's phase event,
-        // recorded at the same point, serves when there is one: each record costs the chain
-        // to phase F a few us)
-        if (!fev) DMF_HIP(hipEventRecord(v->st_b[slot], sl));
-        v->st_b_ev[slot] = fev ? v->f_event : v->st_b[slot];
-        v->st_b_set[slot] = true;
-      }
-      if (slab)
-        hipLaunchKernelGGL((k_bk_fuse_s<kBkRefill, kBkSpread, kBkUnroll>), dim3(nf), dim3(kBkThreads), 0, v->stream, g, bg,
-                           (const uint4*)b.pra, (const uint32_t*)b.prb, (const uint32_t*)b.off, (const uint32_t*)b.cnt,
-                           (const uint2*)b.order, pl.part_max, b.ctl, d_hits, d_misses, st);
-      else
-        hipLaunchKernelGGL((k_bk_fuse<16, 8, 8>), dim3(nf), dim3(kBkThreads), 0, v->stream, g, bg, (const uint4*)b.pra,
-                           (const uint2*)b.prb, (const uint32_t*)b.off, (const uint32_t*)b.cnt,
-                           (const uint32_t*)b.part_pref, b.ctl, d_hits, d_misses, st);
-      DMF_LAUNCH_CHECK();
-      if (staged) DMF_HIP(hipEventRecord(v->st_free[slot], v->stream));  // batch j's phase F
-    }
-    // pass A's statistics summed before the call's own (after phase F: off the chain)
-    if (staged) DMF_HIP(hipStreamWaitEvent(v->stream, v->st_done[slot], 0));
-    if (staged || (v->stage && !capturing)) {  // the slot's last reader (phase F) is enqueued
-      DMF_HIP(hipEventRecord(v->st_free[slot], v->stream));
-      v->st_free_set[slot] = true;
-    }
-  }
   return DMF_OK;
 }
 
@@ -2239,15 +2057,20 @@ static const dmf_fuse_params kDefaultParamsForCheck = {200, 1000, 847, -405, -20
 
 static const char kFuseGridLimit[] = "fusion grid is limited to 2048 cells per axis (fixed-point DDA)";
 
+// What fusion needs of the volume, whatever the ray source
+static int check_fuse_volume(const dmf_volume* v) {
+  DMF_TRY(require_grid_2048(v, kFuseGridLimit));
+  if (tiled_cells(v->geom().n) > (size_t)UINT32_MAX)
+    return fail(DMF_ERR_RANGE, "fusion grid is limited to 2^32 tiled counter cells");
+  return DMF_OK;
+}
+
 static int check_fuse(const dmf_volume* v, const dmf_camera* cam, int P, const dmf_fuse_params* prm) {
   DMF_TRY(require_constructed(v));  // (before the camera: an unconstructed volume is reported first)
   DMF_TRY(check_camera(cam));
   if (!prm) return fail(DMF_ERR_INVALID, "null params");
   if (P <= 0 || P > 65535) return fail(DMF_ERR_INVALID, "pose count %d out of range [1,65535]", P);
-  DMF_TRY(require_grid_2048(v, kFuseGridLimit));
-  if (tiled_cells(v->geom().n) > (size_t)UINT32_MAX)
-    return fail(DMF_ERR_RANGE, "fusion grid is limited to 2^32 tiled counter cells");
-  return DMF_OK;
+  return check_fuse_volume(v);
 }
 
 int check_fuse_call(const dmf_volume* v, const dmf_camera* cam, int P) {
@@ -2263,15 +2086,22 @@ static int check_fuse_points(const dmf_volume* v, int S, int64_t N, const dmf_fu
   if (!prm) return fail(DMF_ERR_INVALID, "null params");
   if (N < 1) return fail(DMF_ERR_INVALID, "point count %lld per scan must be >= 1", (long long)N);
   if (S <= 0 || S > 65535) return fail(DMF_ERR_INVALID, "scan count %d out of range [1,65535]", S);
-  DMF_TRY(require_grid_2048(v, kFuseGridLimit));
-  if (tiled_cells(v->geom().n) > (size_t)UINT32_MAX)
-    return fail(DMF_ERR_RANGE, "fusion grid is limited to 2^32 tiled counter cells");
+  DMF_TRY(check_fuse_volume(v));
   if (N > (int64_t)INT32_MAX - 63) return fail(DMF_ERR_RANGE, "one frame exceeds the 32-bit pair offsets");
   return DMF_OK;
 }
 
 static const char* variant_kernel(int fv) {
   return fv == DMF_FUSE_LDS_BOX ? kNameLds : (fv == DMF_FUSE_CELL_WALK ? kNameCell : kNameSlab);
+}
+
+// The *_reserve calls' budget (0 = keep the volume's)
+static int set_budget(dmf_volume* v, uint64_t max_scratch_bytes) {
+  if (max_scratch_bytes && max_scratch_bytes != v->bk_budget) {
+    DMF_TRY(bk_release(v));  // the slots are re-planned against the new budget
+    v->bk_budget = max_scratch_bytes;
+  }
+  return DMF_OK;
 }
 
 // The scratch of fusion calls of up to P frames of `ppose` packets each (dmf_fuse_reserve,
@@ -2291,15 +2121,274 @@ static int reserve_fusion(dmf_volume* v, int64_t ppose, int P) {
       DMF_TRY(bk_scratch(v, pl, set, 1));
       DMF_TRY(stage_init(v));
       void* t;
-      for (int k = 0; k < 2; ++k) {
-        DMF_TRY(scratch(v, k ? kScStPoses1 : kScStPoses0, sizeof(PoseX) * (size_t)pl.PS, &t));
-        DMF_TRY(scratch(v, k ? kScStStats1 : kScStStats0, sizeof(unsigned long long) * kStatSlots * kStatWidth, &t));
-      }
+      for (int k = 0; k < 2; ++k)
+        for (int buf = kBkPipeBufs; buf < kBkBufCount; ++buf)
+          DMF_TRY(scratch(v, bk_key(buf, k), bk_buf_bytes(pl, buf), &t));
     }
   }
   DMF_HIP(hipStreamSynchronize(v->stream));
   return DMF_OK;
 }
+
+// Tiled counters to the linear (x-major) layout, on the volume's stream
+static int counters_to_linear(dmf_volume* v, const int32_t* d_tiled, int32_t* d_linear) {
+  const int64_t n = (int64_t)v->ncell;
+  hipLaunchKernelGGL(k_counter_layout<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, v->geom(),
+                     d_tiled, d_linear, n);
+  DMF_LAUNCH_CHECK();
+  return DMF_OK;
+}
+
+// The host side of a ray source: the frames of one call, and the device source of the frames
+// from s0 on (k_fuse_l reads all of them, pass A a super-batch), read with the pose table `tab`
+// of those frames.  A source with d_poses builds that table from them (the call's, or a staged
+// super-batch's on the staging stream).
+struct DepthFeed {
+  using Src = DepthSrc;
+  CamP cp;
+  const uint16_t* d_depth;
+  const float* d_poses;
+  int dmin, dmax;
+  int64_t packets() const { return cam_packets(cp); }
+  Src src(int64_t s0, const PoseX* tab) const {
+    return Src{cp, d_depth + (size_t)s0 * cp.H * cp.W, tab, dmin, dmax, (cp.W + 7) / 8};
+  }
+};
+// Points: the scans' origins take the pose table's place, read as the caller wrote them (a
+// staged pass A follows the input stream as it does for depth frames).
+struct PointFeed {
+  using Src = PointSrc;
+  const float* d_xyz;
+  const float* d_origins;
+  int64_t N;
+  static constexpr const float* d_poses = nullptr;
+  int64_t packets() const { return scan_packets(N); }
+  Src src(int64_t s0, const PoseX*) const { return Src{d_xyz + (size_t)s0 * (size_t)N * 3, d_origins + (size_t)s0 * 3, N}; }
+};
+
+// One brick-pipeline call, and the super-batch of it under way: frames [s0, s0 + ps) in staging
+// slot `slot` (serial calls: 0), whose buffers are b and whose events are sl.
+struct BkCall {
+  dmf_volume* v;
+  Geom g;
+  const PoseX* tab;  // the call's pose table (unstaged depth calls)
+  int32_t *d_hits, *d_misses;
+  unsigned long long* st;  // the call's striped statistics (null: none), summed into d_user
+  uint64_t* d_user;
+  bool staged, capturing;
+  BkPlan pl;
+  BkBufs b;
+  unsigned nf = 0;  // phase F's persistent workgroups: one per CU
+  int64_t s0 = 0, ps = 0;
+  int slot = 0;
+  dmf_volume::StageSlot* sl = nullptr;
+  unsigned nwg() const { return (unsigned)(ps * pl.wg_pose); }  // workgroups of passes A / B
+  // small grids: batch cut, brick counts and scan in one launch per batch (k_bk_layout1)
+  bool layout1() const { return pl.bg.nbricks <= kBkLayout1Bricks && ps <= kBkLayout1Poses; }
+
+  // The slot's input ordering and pass A of the super-batch.
+  template <class Feed>
+  int pass_a(const Feed& feed) {
+    using Src = typename Feed::Src;
+    // everything but phase F: the staging stream (pipelined) or the volume's stream
+    const hipStream_t sa = staged ? v->stage : v->stream;
+    unsigned long long* st_a = st;
+    if (staged) {
+      DMF_HIP(hipEventRecord(v->st_in, v->in_stream));
+      DMF_HIP(hipStreamWaitEvent(sa, v->st_in, 0));
+      if (sl->free_set) DMF_HIP(hipStreamWaitEvent(sa, sl->free, 0));
+    }
+    const PoseX* tab_a = tab ? tab + s0 : nullptr;
+    if (staged && feed.d_poses) {  // (a staged depth call's pose table is built here, on the staging stream)
+      void* t;
+      DMF_TRY(scratch(v, bk_key(kBufStPoses, slot), bk_buf_bytes(pl, kBufStPoses), &t));
+      DMF_TRY(pose_table_into(feed.d_poses + (size_t)s0 * 12, (int)ps, (PoseX*)t, sa));
+      tab_a = (const PoseX*)t;
+    }
+    if (staged && st) {
+      void* sbuf;
+      DMF_TRY(scratch(v, bk_key(kBufStStats, slot), bk_buf_bytes(pl, kBufStStats), &sbuf));
+      DMF_HIP(hipMemsetAsync(sbuf, 0, bk_buf_bytes(pl, kBufStStats), sa));
+      st_a = (unsigned long long*)sbuf;
+    }
+    DMF_HIP(hipMemsetAsync(b.pose_cnt, 0, pl.hist_bytes * (size_t)ps, sa));
+    DMF_HIP(hipMemsetAsync(b.pose_pairs, 0, sizeof(unsigned long long) * (size_t)ps, sa));
+    // pass A after the previous super-batch's pass B: it then runs beside that super-batch's
+    // phase F (launched at once, it would run beside pass B instead, and phase F alone); the
+    // pose table and the zeroing above may run beside pass B
+    const dmf_volume::StageSlot& prev = v->slots[slot ^ 1];
+    if (staged && prev.b_set) DMF_HIP(hipStreamWaitEvent(sa, prev.b_ev, 0));
+    BkRaysArgs<Src> ra{g, feed.src(s0, tab_a), (int)pl.ppose, pl.wg_pose, pl.span, pl.bg, b.rays, b.paths, b.pose_cnt,
+                       b.wgb, b.wgl, pl.wgl_stride, b.pose_pairs, st_a, b.ovl, 0};
+    if (pl.hash_log > 0) {
+      // hashed histogram (8 KB: beside phase F's box), then the overflowed workgroups (if any)
+      // with the direct table
+      ra.hash_log = pl.hash_log;
+      DMF_HIP(hipMemsetAsync(b.ovl, 0, sizeof(uint32_t), sa));
+      hipLaunchKernelGGL(k_bk_rays_hash<Src>, dim3(nwg()), dim3(kBkPassThreads), sizeof(uint32_t) << pl.hash_log, sa, ra);
+      DMF_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_bk_rays_recover<Src>, dim3(nf), dim3(kBkPassThreadsBig),
+                         sizeof(uint32_t) * ((pl.bg.nbricks + 1) / 2), sa, ra);
+    } else {
+      hipLaunchKernelGGL((k_bk_rays<true, Src>), dim3(nwg()), dim3(pl.ab_threads),
+                         sizeof(uint32_t) * ((pl.bg.nbricks + 1) / 2), sa, ra);
+    }
+    DMF_LAUNCH_CHECK();
+    if (staged) {
+      // the layout, pass B and phase F on the volume's stream after pass A (event a): pass
+      // B follows the previous call's phase F in stream order (it never ran beside it: pass
+      // A's tail outlasts F), and phase F follows pass B with no cross-stream event (13 -> 7
+      // us per call).  Pass A's statistics are then summed here, on the staging stream
+      // (atomic sums: the previous call's are summed on the volume's stream meanwhile), off
+      // the chain to pass B; event done (after them) orders the input stream, and the volume's
+      // stream after this call's phase F.
+      DMF_HIP(hipEventRecord(sl->a, sa));
+      DMF_HIP(hipStreamWaitEvent(v->stream, sl->a, 0));
+      if (st) DMF_TRY(stats_end(v, st_a, d_user, kStatWidth, nullptr, sa));
+      DMF_HIP(hipEventRecord(sl->done, sa));
+      DMF_HIP(hipStreamWaitEvent(v->in_stream, sl->done, 0));
+    }
+    return DMF_OK;
+  }
+
+  // The device's cut of the super-batch's poses into batches, on the volume's stream (as
+  // everything after pass A); k_bk_layout1 makes it itself, per batch.
+  int batch_cut() {
+    if (!layout1()) {
+      hipLaunchKernelGGL(k_bk_batches, dim3(1), dim3(1024), 0, v->stream, (int)ps, (const unsigned long long*)b.pose_pairs,
+                         (unsigned long long)pl.pair_cap, pl.max_poses, b.bt);
+      DMF_LAUNCH_CHECK();
+    }
+    v->bk_last_bt = b.bt;
+    return DMF_OK;
+  }
+
+  // Batch j of the super-batch: the brick layout, pass B, the phase events and phase F.  Batch
+  // j > 0 reuses the slot's pair records and part queue, so it follows batch j-1's phase F in
+  // stream order.  The host launches jmax triples from the one-pose bound; those past the
+  // device's batch count exit at once (1024^3: jmax 7, one batch).
+  int batch(int64_t j) {
+    const BkGeom& bg = pl.bg;
+    const hipStream_t sj = v->stream;
+    const bool slab = v->fuse_variant != DMF_FUSE_CELL_WALK;
+    // pass B and the brick scan, each one launch whatever the variant / grid size
+    auto pass_b = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(nwg()), dim3(pl.ab_threads), pl.hist_bytes, sj, (int)pl.ppose, pl.wg_pose, pl.span,
+                         bg, (const ulonglong2*)b.rays, (const uint64_t*)b.paths, (const uint32_t*)b.off,
+                         (const uint32_t*)b.pose_base, (const uint32_t*)b.wgb, (const uint32_t*)b.bt, (int)j,
+                         (const uint32_t*)b.wgl, pl.wgl_stride, b.pra, b.prb, b.ctl, v->d_fault,
+                         (int)std::min<int64_t>(v->knob[DMF_KNOB_FAULT_INJECT], 1 << 20), st);
+    };
+    auto scan = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(1), dim3(1024), 0, sj, bg.nbricks, (const uint32_t*)b.cnt, b.off, b.part_pref,
+                         b.ctl, b.order, pl.part_max, (const uint32_t*)b.bt, (int)j, pl.split_cu);
+    };
+    // (the scan zeroes phase F's queue head: no memset of ctl)
+    if (layout1()) {
+      hipLaunchKernelGGL(k_bk_layout1, dim3(1), dim3(1024), 0, sj, (int)ps, (const unsigned long long*)b.pose_pairs,
+                         (unsigned long long)pl.pair_cap, pl.max_poses, b.bt, bg.nbricks, (int)j,
+                         (const uint32_t*)b.pose_cnt, b.pose_base, b.cnt, b.off, b.part_pref, b.ctl, b.order,
+                         pl.part_max, pl.split_cu);
+    } else {
+      hipLaunchKernelGGL(k_bk_batch_counts, dim3((unsigned)((bg.nbricks + 255) / 256)), dim3(256), 0, sj,
+                         bg.nbricks, (int)j, (const uint32_t*)b.bt, (const uint32_t*)b.pose_cnt, b.pose_base, b.cnt);
+      DMF_LAUNCH_CHECK();
+      if (bg.nbricks > 4096) scan(k_bk_scan<true>);
+      else scan(k_bk_scan<false>);
+    }
+    DMF_LAUNCH_CHECK();
+    if (slab) pass_b(k_bk_pairs<true>);
+    else pass_b(k_bk_pairs<false>);
+    DMF_LAUNCH_CHECK();
+    // the call's phase F begins (not while capturing: the record would become a graph node
+    // and the caller's event would never be re-recorded by the graph's launches)
+    const bool fev = v->f_event && !capturing && s0 == 0 && j == 0;
+    if (fev) DMF_HIP(hipEventRecord(v->f_event, v->stream));
+    if (staged && j == 0) {
+      // pass B done: the next super-batch's pass A waits for it (the caller's phase event,
+      // recorded at the same point, serves when there is one: each record costs the chain
+      // to phase F a few us)
+      if (!fev) DMF_HIP(hipEventRecord(sl->b, sj));
+      sl->b_ev = fev ? v->f_event : sl->b;
+      sl->b_set = true;
+    }
+    if (slab)
+      hipLaunchKernelGGL((k_bk_fuse_s<kBkRefill, kBkSpread, kBkUnroll>), dim3(nf), dim3(kBkThreads), 0, v->stream, g, bg,
+                         (const uint4*)b.pra, (const uint32_t*)b.prb, (const uint32_t*)b.off, (const uint32_t*)b.cnt,
+                         (const uint2*)b.order, pl.part_max, b.ctl, d_hits, d_misses, st);
+    else
+      hipLaunchKernelGGL((k_bk_fuse<kCellRefill, kCellOrder, kCellUnroll>), dim3(nf), dim3(kBkThreads), 0, v->stream, g,
+                         bg, (const uint4*)b.pra, (const uint2*)b.prb, (const uint32_t*)b.off, (const uint32_t*)b.cnt,
+                         (const uint32_t*)b.part_pref, b.ctl, d_hits, d_misses, st);
+    DMF_LAUNCH_CHECK();
+    if (staged) DMF_HIP(hipEventRecord(sl->free, v->stream));  // batch j's phase F
+    return DMF_OK;
+  }
+
+  // The call: the plan, then per super-batch its slot, the three steps above and the slot's release.
+  template <class Feed>
+  int fuse_bricks(const Feed& feed, int P) {
+    DMF_TRY(bk_plan(v, feed.packets(), g, P, pl));
+    DMF_TRY(bk_attributes());
+    DMF_TRY(fault_words(v));
+    if (staged) DMF_TRY(stage_init(v));
+    // pass A with 16-bit histogram counts (a workgroup's pairs per brick <= span * 64 rays; the
+    // plan holds span <= 1023)
+    if ((int64_t)pl.span * 64 > 65535) return fail(DMF_ERR_RANGE, "pass A span %d exceeds 16-bit counts", pl.span);
+    nf = (unsigned)cu_count(v->device);
+    for (s0 = 0; s0 < P; s0 += pl.PS) {
+      ps = std::min<int64_t>(pl.PS, P - s0);
+      slot = staged ? v->st_slot : 0;
+      sl = &v->slots[slot];
+      DMF_TRY(bk_scratch(v, pl, b, slot));
+      if (staged) v->st_slot ^= 1;
+      DMF_TRY(pass_a(feed));
+      DMF_TRY(batch_cut());
+      const int64_t jm = pl.jmax(ps);
+      for (int64_t j = 0; j < jm; ++j) DMF_TRY(batch(j));
+      // pass A's statistics summed before the call's own (after phase F: off the chain)
+      if (staged) DMF_HIP(hipStreamWaitEvent(v->stream, sl->done, 0));
+      if (staged || (v->stage && !capturing)) {  // the slot's last reader (phase F) is enqueued
+        DMF_HIP(hipEventRecord(sl->free, v->stream));
+        sl->free_set = true;
+      }
+    }
+    return DMF_OK;
+  }
+};
+
+// dmf_fuse_depth_device / dmf_fuse_points_device, after their checks, over P frames of `feed`;
+// allow_stage = false for the host forms (their inputs are uploaded on the volume's stream)
+template <class Feed>
+static int fuse_call(dmf_volume* v, const Feed& feed, int32_t P, int32_t* d_hits, int32_t* d_misses, uint64_t* d_stats,
+                     bool allow_stage) {
+  const Geom g = v->geom();
+  const bool brick = use_bricks(v, g);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  DMF_HIP(hipStreamIsCapturing(v->stream, &cs));
+  const bool capturing = cs != hipStreamCaptureStatusNone;
+  const bool staged = brick && allow_stage && v->pipelined && !capturing;
+  PoseX* tab = nullptr;
+  if (feed.d_poses && !staged) DMF_TRY(pose_table(v, feed.d_poses, P, true, &tab));
+  unsigned long long* st = nullptr;
+  if (d_stats) DMF_TRY(stats_begin(v, &st));
+  if (brick) {
+    v->last_kernel = variant_kernel(v->fuse_variant);
+    BkCall c{v, g, tab, d_hits, d_misses, st, d_stats, staged, capturing};
+    DMF_TRY(c.fuse_bricks(feed, P));
+  } else {
+    if (v->f_event && !capturing) DMF_HIP(hipEventRecord(v->f_event, v->stream));
+    hipLaunchKernelGGL((k_fuse_l<kLdsS, kLdsBox, typename Feed::Src>), dim3((unsigned)feed.packets(), (unsigned)P),
+                       dim3(64), 0, v->stream, g, feed.src(0, tab), d_hits, d_misses, st);
+    DMF_LAUNCH_CHECK();
+    v->last_kernel = kNameLds;
+  }
+  // (brick pipeline: the layout faults not yet reported go to d_stats[3])
+  if (d_stats) DMF_TRY(stats_end(v, st, d_stats, kStatWidth, brick ? v->d_fault : nullptr));
+  DMF_LAUNCH_CHECK();
+  return DMF_OK;
+}
+
 
 }  // namespace dmf
 
@@ -2353,10 +2442,7 @@ int dmf_volume_get_knob(const dmf_volume* v, int32_t knob, int64_t* value) {
 int dmf_fuse_reserve(dmf_volume* v, const dmf_camera* cam, int32_t P, uint64_t max_scratch_bytes) {
   DMF_API_BEGIN
   DMF_TRY(check_fuse(v, cam, P, &kDefaultParamsForCheck));
-  if (max_scratch_bytes && max_scratch_bytes != v->bk_budget) {
-    DMF_TRY(bk_release(v));  // the slots are re-planned against the new budget
-    v->bk_budget = max_scratch_bytes;
-  }
+  DMF_TRY(set_budget(v, max_scratch_bytes));
   const CamP cp = cam_params(cam);
   void* tab;
   DMF_TRY(scratch(v, kScPoses, sizeof(PoseX) * (size_t)P, &tab));
@@ -2367,10 +2453,7 @@ int dmf_fuse_reserve(dmf_volume* v, const dmf_camera* cam, int32_t P, uint64_t m
 int dmf_fuse_points_reserve(dmf_volume* v, int32_t S, int64_t N, uint64_t max_scratch_bytes) {
   DMF_API_BEGIN
   DMF_TRY(check_fuse_points(v, S, N, &kDefaultParamsForCheck));
-  if (max_scratch_bytes && max_scratch_bytes != v->bk_budget) {
-    DMF_TRY(bk_release(v));  // the slots are re-planned against the new budget
-    v->bk_budget = max_scratch_bytes;
-  }
+  DMF_TRY(set_budget(v, max_scratch_bytes));
   return reserve_fusion(v, scan_packets(N), S);
   DMF_API_END
 }
@@ -2427,11 +2510,7 @@ int dmf_fuse_counters_to_linear_device(dmf_volume* v, const int32_t* d_tiled, in
   DMF_API_BEGIN
   DMF_TRY(require_constructed(v));
   if (!d_tiled || !d_linear) return fail(DMF_ERR_INVALID, "null device buffer");
-  const int64_t n = (int64_t)v->ncell;
-  hipLaunchKernelGGL(k_counter_layout<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, v->geom(),
-                     d_tiled, d_linear, n);
-  DMF_LAUNCH_CHECK();
-  return DMF_OK;
+  return counters_to_linear(v, d_tiled, d_linear);
   DMF_API_END
 }
 
@@ -2440,8 +2519,8 @@ int dmf_fuse_set_phase_event(dmf_volume* v, void* event) {
   if (!v) return fail(DMF_ERR_INVALID, "null volume");
   // the next pass A no longer waits on the caller's old event (the wait only schedules it
   // beside phase F: nothing depends on it, and the event may be destroyed after this)
-  for (int k = 0; k < 2; ++k)
-    if (v->st_b_ev[k] == v->f_event) v->st_b_set[k] = false;
+  for (dmf_volume::StageSlot& s : v->slots)
+    if (s.b_ev == v->f_event) s.b_set = false;
   v->f_event = (hipEvent_t)event;
   return DMF_OK;
   DMF_API_END
@@ -2459,75 +2538,29 @@ int dmf_fuse_set_input_stream(dmf_volume* v, void* stream) {
   DMF_API_END
 }
 
+int dmf_fuse_depth_device(dmf_volume* v, const dmf_camera* cam, const uint16_t* d_depth, const float* d_poses,
+                          int32_t P, const dmf_fuse_params* prm, int32_t* d_hits, int32_t* d_misses,
+                          uint64_t* d_stats) {
+  DMF_API_BEGIN
+  DMF_TRY(check_fuse(v, cam, P, prm));
+  if (!d_depth || !d_poses || !d_hits || !d_misses) return fail(DMF_ERR_INVALID, "null device buffer");
+  const DepthFeed feed{cam_params(cam), d_depth, d_poses, prm->dmin_mm, prm->dmax_mm};
+  return fuse_call(v, feed, P, d_hits, d_misses, d_stats, true);
+  DMF_API_END
+}
+
+int dmf_fuse_points_device(dmf_volume* v, const float* d_xyz, const float* d_origins, int32_t S, int64_t N,
+                           const dmf_fuse_params* prm, int32_t* d_hits, int32_t* d_misses, uint64_t* d_stats) {
+  DMF_API_BEGIN
+  if (!d_xyz || !d_origins || !d_hits || !d_misses) return fail(DMF_ERR_INVALID, "null device buffer");
+  DMF_TRY(check_fuse_points(v, S, N, prm));
+  return fuse_call(v, PointFeed{d_xyz, d_origins, N}, S, d_hits, d_misses, d_stats, true);
+  DMF_API_END
+}
+
 }  // extern "C"
 
 namespace dmf {
-// dmf_fuse_depth_device; allow_stage = false for the host form (its inputs are uploaded on
-// the volume's stream)
-static int fuse_device(dmf_volume* v, const dmf_camera* cam, const uint16_t* d_depth, const float* d_poses, int32_t P,
-                       const dmf_fuse_params* prm, int32_t* d_hits, int32_t* d_misses, uint64_t* d_stats,
-                       bool allow_stage) {
-  DMF_TRY(check_fuse(v, cam, P, prm));
-  if (!d_depth || !d_poses || !d_hits || !d_misses) return fail(DMF_ERR_INVALID, "null device buffer");
-  const CamP cp = cam_params(cam);
-  const Geom g = v->geom();
-  const bool brick = use_bricks(v, g);
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  DMF_HIP(hipStreamIsCapturing(v->stream, &cs));
-  const bool capturing = cs != hipStreamCaptureStatusNone;
-  const bool staged = brick && allow_stage && v->pipelined && !capturing;
-  PoseX* tab = nullptr;
-  if (!staged) DMF_TRY(pose_table(v, d_poses, P, true, &tab));
-  unsigned long long* st = nullptr;
-  if (d_stats) DMF_TRY(stats_begin(v, &st));
-  if (brick) {
-    v->last_kernel = variant_kernel(v->fuse_variant);
-    const DepthFeed feed{cp, d_depth, tab, d_poses, prm->dmin_mm, prm->dmax_mm};
-    DMF_TRY(fuse_bricks(v, feed, g, P, d_hits, d_misses, st, d_stats, staged, capturing));
-  } else {
-    const int pkx = (cp.W + 7) / 8;
-    if (v->f_event && !capturing) DMF_HIP(hipEventRecord(v->f_event, v->stream));
-    const DepthSrc src{cp, d_depth, tab, prm->dmin_mm, prm->dmax_mm, pkx};
-    hipLaunchKernelGGL((k_fuse_l<12, 1280, DepthSrc>), dim3((unsigned)cam_packets(cp), (unsigned)P), dim3(64), 0,
-                       v->stream, g, src, d_hits, d_misses, st);
-    DMF_LAUNCH_CHECK();
-    v->last_kernel = kNameLds;
-  }
-  // (brick pipeline: the layout faults not yet reported go to d_stats[3])
-  if (d_stats) DMF_TRY(stats_end(v, st, d_stats, kStatWidth, brick ? v->d_fault : nullptr));
-  DMF_LAUNCH_CHECK();
-  return DMF_OK;
-}
-
-// dmf_fuse_points_device: fuse_device with the point source (no pose table: pass A and k_fuse_l
-// read the origins as they are); the caller has run check_fuse_points.
-static int fuse_points_dev(dmf_volume* v, const float* d_xyz, const float* d_origins, int32_t S, int64_t N,
-                           int32_t* d_hits, int32_t* d_misses, uint64_t* d_stats, bool allow_stage) {
-  const Geom g = v->geom();
-  const bool brick = use_bricks(v, g);
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  DMF_HIP(hipStreamIsCapturing(v->stream, &cs));
-  const bool capturing = cs != hipStreamCaptureStatusNone;
-  const bool staged = brick && allow_stage && v->pipelined && !capturing;
-  unsigned long long* st = nullptr;
-  if (d_stats) DMF_TRY(stats_begin(v, &st));
-  if (brick) {
-    v->last_kernel = variant_kernel(v->fuse_variant);
-    const PointFeed feed{d_xyz, d_origins, N};
-    DMF_TRY(fuse_bricks(v, feed, g, S, d_hits, d_misses, st, d_stats, staged, capturing));
-  } else {
-    if (v->f_event && !capturing) DMF_HIP(hipEventRecord(v->f_event, v->stream));
-    const PointSrc src{d_xyz, d_origins, N};
-    hipLaunchKernelGGL((k_fuse_l<12, 1280, PointSrc>), dim3((unsigned)scan_packets(N), (unsigned)S), dim3(64), 0,
-                       v->stream, g, src, d_hits, d_misses, st);
-    DMF_LAUNCH_CHECK();
-    v->last_kernel = kNameLds;
-  }
-  if (d_stats) DMF_TRY(stats_end(v, st, d_stats, kStatWidth, brick ? v->d_fault : nullptr));
-  DMF_LAUNCH_CHECK();
-  return DMF_OK;
-}
-
 // Reads and clears the volume's layout-fault count (synchronises the volume's streams).
 static int take_faults(dmf_volume* v, uint64_t* faults) {
   uint32_t f = 0;
@@ -2552,64 +2585,64 @@ struct HostCounters {
   uint64_t* ds;      // 8 statistics counters
   int32_t* lin;      // one linear counter array (staging)
 };
-// The host forms' counters: the caller's linear x-major hits / misses uploaded into zeroed tiled
-// device counters (the call accumulates onto them), zeroed statistics ...
-static int host_counters_up(dmf_volume* v, const int32_t* hits, const int32_t* misses, HostCounters& hc) {
+// The caller's linear x-major hits / misses uploaded into zeroed tiled device counters (hc.dh,
+// hc.dm; through the staging array hc.lin)
+static int upload_counters(dmf_volume* v, const int32_t* hits, const int32_t* misses, HostCounters& hc) {
   const Geom g = v->geom();
   const size_t nt = tiled_cells(g.n);
   const int64_t n = (int64_t)v->ncell;
-  void *dh, *dm, *ds, *lin;
+  void *dh, *dm, *lin;
   DMF_TRY(scratch(v, kScOut0, sizeof(int32_t) * nt, &dh));
   DMF_TRY(scratch(v, kScOut1, sizeof(int32_t) * nt, &dm));
-  DMF_TRY(scratch(v, kScOut2, sizeof(uint64_t) * 8, &ds));
   DMF_TRY(scratch(v, kScOut3, sizeof(int32_t) * v->ncell, &lin));
   DMF_HIP(hipMemsetAsync(dh, 0, sizeof(int32_t) * nt, v->stream));
   DMF_HIP(hipMemsetAsync(dm, 0, sizeof(int32_t) * nt, v->stream));
   const dim3 lg((unsigned)((n + 255) / 256));
-  // accumulate onto the caller's linear counters
   DMF_HIP(hipMemcpyAsync(lin, hits, sizeof(int32_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
   hipLaunchKernelGGL(k_counter_layout<false>, lg, dim3(256), 0, v->stream, g, (const int32_t*)lin, (int32_t*)dh, n);
   DMF_LAUNCH_CHECK();
   DMF_HIP(hipMemcpyAsync(lin, misses, sizeof(int32_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
   hipLaunchKernelGGL(k_counter_layout<false>, lg, dim3(256), 0, v->stream, g, (const int32_t*)lin, (int32_t*)dm, n);
   DMF_LAUNCH_CHECK();
-  DMF_HIP(hipMemsetAsync(ds, 0, sizeof(uint64_t) * 8, v->stream));
-  hc = HostCounters{(int32_t*)dh, (int32_t*)dm, (uint64_t*)ds, (int32_t*)lin};
+  hc.dh = (int32_t*)dh;
+  hc.dm = (int32_t*)dm;
+  hc.lin = (int32_t*)lin;
   return DMF_OK;
 }
 
-// ... and back after the call: linear counters, the layout check, stats[3] += {updates, rays, hits}
+// The host forms' counters back after the call: linear counters, the layout check, stats[3] += {updates, rays, hits}
 static int host_counters_down(dmf_volume* v, const HostCounters& hc, int32_t* hits, int32_t* misses, int64_t* stats) {
-  const Geom g = v->geom();
-  const int64_t n = (int64_t)v->ncell;
-  const dim3 lg((unsigned)((n + 255) / 256));
-  void *const dh = hc.dh, *const dm = hc.dm, *const ds = hc.ds, *const lin = hc.lin;
   uint64_t st[4];
-  hipLaunchKernelGGL(k_counter_layout<true>, lg, dim3(256), 0, v->stream, g, (const int32_t*)dh, (int32_t*)lin, n);
-  DMF_LAUNCH_CHECK();
-  DMF_HIP(hipMemcpyAsync(hits, lin, sizeof(int32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
+  DMF_TRY(counters_to_linear(v, hc.dh, hc.lin));
+  DMF_HIP(hipMemcpyAsync(hits, hc.lin, sizeof(int32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
   DMF_HIP(hipStreamSynchronize(v->stream));
-  hipLaunchKernelGGL(k_counter_layout<true>, lg, dim3(256), 0, v->stream, g, (const int32_t*)dm, (int32_t*)lin, n);
-  DMF_LAUNCH_CHECK();
-  DMF_HIP(hipMemcpyAsync(misses, lin, sizeof(int32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
-  DMF_HIP(hipMemcpyAsync(st, ds, sizeof(st), hipMemcpyDeviceToHost, v->stream));
+  DMF_TRY(counters_to_linear(v, hc.dm, hc.lin));
+  DMF_HIP(hipMemcpyAsync(misses, hc.lin, sizeof(int32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
+  DMF_HIP(hipMemcpyAsync(st, hc.ds, sizeof(st), hipMemcpyDeviceToHost, v->stream));
   DMF_HIP(hipStreamSynchronize(v->stream));
   DMF_TRY(take_faults(v, nullptr));
   if (stats)
     for (int k = 0; k < 3; ++k) stats[k] += (int64_t)st[k];
   return DMF_OK;
 }
+
+// The host forms (dmf_fuse_depth, dmf_fuse_points), after their checks and the upload of their
+// inputs on the volume's stream: the call accumulates onto the caller's counters
+// (upload_counters), with zeroed statistics, and hands them back (host_counters_down).
+template <class Feed>
+static int fuse_host(dmf_volume* v, const Feed& feed, int32_t P, int32_t* hits, int32_t* misses, int64_t* stats) {
+  HostCounters hc;
+  void* ds;
+  DMF_TRY(scratch(v, kScOut2, sizeof(uint64_t) * 8, &ds));
+  DMF_TRY(upload_counters(v, hits, misses, hc));
+  DMF_HIP(hipMemsetAsync(ds, 0, sizeof(uint64_t) * 8, v->stream));
+  hc.ds = (uint64_t*)ds;
+  DMF_TRY(fuse_call(v, feed, P, hc.dh, hc.dm, hc.ds, false));
+  return host_counters_down(v, hc, hits, misses, stats);
+}
 }  // namespace dmf
 
 extern "C" {
-
-int dmf_fuse_depth_device(dmf_volume* v, const dmf_camera* cam, const uint16_t* d_depth, const float* d_poses,
-                          int32_t P, const dmf_fuse_params* prm, int32_t* d_hits, int32_t* d_misses,
-                          uint64_t* d_stats) {
-  DMF_API_BEGIN
-  return fuse_device(v, cam, d_depth, d_poses, P, prm, d_hits, d_misses, d_stats, true);
-  DMF_API_END
-}
 
 int dmf_fuse_depth(dmf_volume* v, const dmf_camera* cam, const uint16_t* depth, const float* poses, int32_t P,
                    const dmf_fuse_params* prm, int32_t* hits, int32_t* misses, int64_t* stats) {
@@ -2622,19 +2655,8 @@ int dmf_fuse_depth(dmf_volume* v, const dmf_camera* cam, const uint16_t* depth, 
   DMF_TRY(scratch(v, kScHost2, sizeof(float) * 12 * P, &dp));
   DMF_HIP(hipMemcpyAsync(dd, depth, sizeof(uint16_t) * HW * P, hipMemcpyHostToDevice, v->stream));
   DMF_HIP(hipMemcpyAsync(dp, poses, sizeof(float) * 12 * P, hipMemcpyHostToDevice, v->stream));
-  HostCounters hc;
-  DMF_TRY(host_counters_up(v, hits, misses, hc));
-  DMF_TRY(fuse_device(v, cam, (const uint16_t*)dd, (const float*)dp, P, prm, hc.dh, hc.dm, hc.ds, false));
-  return host_counters_down(v, hc, hits, misses, stats);
-  DMF_API_END
-}
-
-int dmf_fuse_points_device(dmf_volume* v, const float* d_xyz, const float* d_origins, int32_t S, int64_t N,
-                           const dmf_fuse_params* prm, int32_t* d_hits, int32_t* d_misses, uint64_t* d_stats) {
-  DMF_API_BEGIN
-  if (!d_xyz || !d_origins || !d_hits || !d_misses) return fail(DMF_ERR_INVALID, "null device buffer");
-  DMF_TRY(check_fuse_points(v, S, N, prm));
-  return fuse_points_dev(v, d_xyz, d_origins, S, N, d_hits, d_misses, d_stats, true);
+  const DepthFeed feed{cam_params(cam), (const uint16_t*)dd, (const float*)dp, prm->dmin_mm, prm->dmax_mm};
+  return fuse_host(v, feed, P, hits, misses, stats);
   DMF_API_END
 }
 
@@ -2649,10 +2671,7 @@ int dmf_fuse_points(dmf_volume* v, const float* xyz, const float* origins, int32
   DMF_TRY(scratch(v, kScHost2, sizeof(float) * 3 * (size_t)S, &dor));
   DMF_HIP(hipMemcpyAsync(dx, xyz, nx, hipMemcpyHostToDevice, v->stream));
   DMF_HIP(hipMemcpyAsync(dor, origins, sizeof(float) * 3 * (size_t)S, hipMemcpyHostToDevice, v->stream));
-  HostCounters hc;
-  DMF_TRY(host_counters_up(v, hits, misses, hc));
-  DMF_TRY(fuse_points_dev(v, (const float*)dx, (const float*)dor, S, N, hc.dh, hc.dm, hc.ds, false));
-  return host_counters_down(v, hc, hits, misses, stats);
+  return fuse_host(v, PointFeed{(const float*)dx, (const float*)dor, N}, S, hits, misses, stats);
   DMF_API_END
 }
 
@@ -2679,25 +2698,11 @@ int dmf_fuse_finalize(dmf_volume* v, const int32_t* hits, const int32_t* misses,
   DMF_API_BEGIN
   DMF_TRY(require_constructed(v));
   if (!prm || !hits || !misses || !out) return fail(DMF_ERR_INVALID, "null argument");
-  const Geom g = v->geom();
-  const size_t nt = tiled_cells(g.n);
-  const int64_t n = (int64_t)v->ncell;
-  void *dh, *dm, *dout, *lin;
-  DMF_TRY(scratch(v, kScOut0, sizeof(int32_t) * nt, &dh));
-  DMF_TRY(scratch(v, kScOut1, sizeof(int32_t) * nt, &dm));
+  void* dout;
   DMF_TRY(scratch(v, kScOut2, sizeof(int16_t) * v->ncell + 32, &dout));
-  DMF_TRY(scratch(v, kScOut3, sizeof(int32_t) * v->ncell, &lin));
-  const dim3 lg((unsigned)((n + 255) / 256));
-  DMF_HIP(hipMemsetAsync(dh, 0, sizeof(int32_t) * nt, v->stream));
-  DMF_HIP(hipMemsetAsync(dm, 0, sizeof(int32_t) * nt, v->stream));
-  DMF_HIP(hipMemcpyAsync(lin, hits, sizeof(int32_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
-  hipLaunchKernelGGL(k_counter_layout<false>, lg, dim3(256), 0, v->stream, g, (const int32_t*)lin, (int32_t*)dh, n);
-  DMF_LAUNCH_CHECK();
-  DMF_HIP(hipStreamSynchronize(v->stream));
-  DMF_HIP(hipMemcpyAsync(lin, misses, sizeof(int32_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
-  hipLaunchKernelGGL(k_counter_layout<false>, lg, dim3(256), 0, v->stream, g, (const int32_t*)lin, (int32_t*)dm, n);
-  DMF_LAUNCH_CHECK();
-  DMF_TRY(dmf_fuse_finalize_device(v, (const int32_t*)dh, (const int32_t*)dm, prm, (int16_t*)dout));
+  HostCounters hc{};
+  DMF_TRY(upload_counters(v, hits, misses, hc));
+  DMF_TRY(dmf_fuse_finalize_device(v, hc.dh, hc.dm, prm, (int16_t*)dout));
   DMF_HIP(hipMemcpyAsync(out, dout, sizeof(int16_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
   DMF_HIP(hipStreamSynchronize(v->stream));
   return DMF_OK;

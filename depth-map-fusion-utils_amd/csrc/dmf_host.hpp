@@ -51,28 +51,33 @@ int require_grid_2048(const dmf_volume* v, const char* text);
 int scratch(dmf_volume* v, int k, size_t bytes, void** out);
 // The fused grid's consumers, host forms: the caller's int16 grid into slot kScOut2 (on the stream).
 int upload_grid(dmf_volume* v, const int16_t* logodds, void** d_grid);
+// The brick pipeline's buffers (dmf_fuse.hip bk_buf_bytes states each one's size): every buffer
+// exists once per staging slot of pipelined fusion; serial calls use slot 0.
+enum BkBuf {
+  kBufRays,                   // ray records, then the crossing paths
+  kBufPairsA, kBufPairsB,     // pair records: the 16-byte half; the slab word (4 bytes) or the cell walk's uint2 (8)
+  kBufBricks, kBufCtl,        // brick counts | offsets | part prefix | part order; phase F's queue control words
+  kBufWgBase, kBufWgList,     // per-workgroup brick bases and touched-brick lists
+  kBufPoseCnt, kBufPoseBase,  // per-pose brick counts and bases
+  kBufBatch, kBufOvl,         // pose pair counts, then the batch table; pass A's hashed-histogram overflow list
+  kBufStPoses, kBufStStats,   // requested on demand: a staged depth call's pose table, a staged call's pass-A statistics
+  kBkBufCount, kBkPipeBufs = kBufStPoses  // [0, kBkPipeBufs): what every call uses (bk_scratch)
+};
 enum ScratchSlot {
   kScPoses = 0, kScHost0, kScHost1, kScHost2, kScOut0, kScOut1, kScOut2, kScOut3, kScTmp, kScSort0,
   kScSort1, kScSort2, kScSort3, kScCount, kScStats,
-  // brick-owned fusion (dmf_fuse.hip)
-  kScBkRays, kScBkPairs, kScBkPairsB, kScBkBricks, kScBkWgBase, kScBkCtl, kScBkPoseCnt, kScBkPoseBase, kScBkBatch,
-  kScBkWgList,
-  // the second staging slot of pipelined fusion (dmf_fuse_set_input_stream) and the
-  // per-slot pose tables / pass-A statistics
-  kScBkRays1, kScBkWgBase1, kScBkWgList1, kScBkPoseCnt1, kScBkBatch1, kScStPoses0, kScStPoses1, kScStStats0,
-  kScStStats1,
-  // ... and, when pass B is staged as well, the second slot's brick layout and pair records
-  kScBkBricks1, kScBkCtl1, kScBkPairs1, kScBkPairsB1, kScBkPoseBase1,
   kScOgP0, kScOgP1, kScOgFinal, kScOgOcc,  // OccupancyGrid reorganization (dmf_ogrid.hip)
   kScRevItems,  // reverseRayTraceFast's item-ordered (spatial order) result masks (dmf_trace.hip)
-  kScBkOvf, kScBkOvf1,  // pass A's hashed-histogram overflow lists, per staging slot (dmf_fuse.hip)
   kScRcFine, kScRcCoarse,  // the log-odds ray-cast's solid mask and its tile + brick levels (dmf_raycast.hip)
   // surface extraction (dmf_surface.hip): the solid, free and surface masks, the per-row counts
   // and their scan, the {surface, solid} counters, and the host forms' output staging
   kScSfSolid, kScSfFree, kScSfSurf, kScSfCounts, kScSfBases, kScSfTotals, kScSfHash, kScSfXyz, kScSfNrm,
   // the distance field (dmf_distance.hip): the y / x passes' envelope stacks, and the host forms' field
-  kScDfStack, kScDfDist
+  kScDfStack, kScDfDist,
+  // brick-owned fusion (dmf_fuse.hip): one block, buffer b of staging slot s at bk_key(b, s)
+  kScBkFirst, kScBkEnd = kScBkFirst + 2 * kBkBufCount
 };
+inline int bk_key(int buf, int slot) { return kScBkFirst + slot * kBkBufCount + buf; }
 
 // Striped statistics: kernels add into slot (block % kStatSlots) of a zeroed buffer
 // of kStatSlots x kStatWidth counters (one hot address per counter serialises at the

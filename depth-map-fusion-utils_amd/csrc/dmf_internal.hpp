@@ -259,14 +259,16 @@ struct dmf_volume {
   bool pipelined = false;
   hipStream_t in_stream = nullptr;  // the caller's input stream
   hipStream_t stage = nullptr;      // staging stream (created on first use)
-  hipEvent_t st_in = nullptr, st_done[2] = {nullptr, nullptr}, st_free[2] = {nullptr, nullptr};
-  bool st_free_set[2] = {false, false};
-  // pass B of the slot's call launched (the next call's pass A waits for it: it then runs beside
-  // that call's phase F)
-  hipEvent_t st_b[2] = {nullptr, nullptr};
-  hipEvent_t st_b_ev[2] = {nullptr, nullptr};  // the event that marks it (st_b, or the caller's phase event)
-  hipEvent_t st_a[2] = {nullptr, nullptr};  // the slot's pass A done (before its statistics' sum)
-  bool st_b_set[2] = {false, false};
+  hipEvent_t st_in = nullptr;       // the caller's inputs, as recorded on in_stream
+  struct StageSlot {
+    hipEvent_t done = nullptr;  // the slot's pass A and its statistics' sum
+    hipEvent_t free = nullptr;  // the slot's last reader (phase F); waited for when free_set
+    hipEvent_t a = nullptr;     // the slot's pass A done (before its statistics' sum)
+    // pass B of the slot's call launched (the next call's pass A waits for it when b_set: it then
+    // runs beside that call's phase F), and the event that marks it (b, or the caller's phase event)
+    hipEvent_t b = nullptr, b_ev = nullptr;
+    bool free_set = false, b_set = false;
+  } slots[2];
   hipEvent_t f_event = nullptr;  // caller's phase-F event (dmf_fuse_set_phase_event)
   int st_slot = 0;
   // device-side layout check of the brick pipeline (dmf_fuse_status): [0] disagreements since

@@ -173,7 +173,7 @@ def test_serial_then_pipelined_without_sync():
     (the serial call is held back by a ~0.5 s spin kernel queued ahead of it, so an unordered
     pass A would overwrite its records).  The mode switch orders it: it frees and re-plans the
     fusion scratch after the volume's streams drain, and staged calls wait for the serial
-    slot's last reader (st_free[0]).  Counters equal an all-serial volume's."""
+    slot's last reader (slots[0].free).  Counters equal an all-serial volume's."""
     poses, depth = _frames(9, seed=5)
     hs, ms, ss = _run(256, poses, depth, 3, pipelined=False)
     v = _Vol(256, 3)
