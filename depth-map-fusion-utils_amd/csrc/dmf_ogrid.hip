@@ -31,6 +31,8 @@ struct dmf_ogrid {
   float* d_centroid = nullptr;  // 3 per voxel
   int32_t* d_count = nullptr;
   uint8_t* d_flags = nullptr;   // bit 0 occupied, bit 1 normal_found
+  int32_t round_cap = 0;        // dmf_diag.h: cap of the reorganization's rounds, 0 = kMaxRounds
+  int32_t reorg_rounds = 0;     // dmf_diag.h: rounds of the latest mode-2/3 download, -1 = serial fallback
 };
 
 namespace dmf {
@@ -43,8 +45,10 @@ struct OGeom {
 __device__ inline bool og_valid(const OGeom& g, int x, int y, int z) {  // OccupancyGrid.hpp:399-402
   return x < g.n[0] && y < g.n[1] && z < g.n[2] && x >= 0 && y >= 0 && z >= 0;
 }
-__device__ inline int og_coord(const OGeom& g, int a, float p) {  // :373-379
-  return (int)floor(((double)p - g.mn[a]) / g.res[a]);
+// :373-379; the int conversion as the host's cvttsd2si makes it: a NaN or out-of-range quotient
+// gives INT_MIN (the device's own conversion gives 0 for NaN, a valid coordinate)
+__device__ inline int og_coord(const OGeom& g, int a, float p) {
+  return to_int_x86(floor(((double)p - g.mn[a]) / g.res[a]));
 }
 
 // Events (voxel << 32 | point) of points [0, n), stride = floats per point; the order
@@ -398,11 +402,12 @@ static int og_reorganize(dmf_ogrid* g, int clean, OgS** F_out, uint8_t** occ_out
   DMF_LAUNCH_CHECK();
   DMF_HIP(hipMemcpyAsync(cur, init, sizeof(OgS) * n, hipMemcpyDeviceToDevice, v->stream));
   constexpr int kMaxRounds = 64;
+  const int cap = g->round_cap > 0 ? g->round_cap : kMaxRounds;
   unsigned long long* keys = nullptr;
   unsigned long long ne = 0;
   int r = 0;
   bool settled = false;
-  for (; r < kMaxRounds && !settled; ++r) {
+  for (; r < cap && !settled; ++r) {
     DMF_HIP(hipMemsetAsync(cnt, 0, 16, v->stream));
     hipLaunchKernelGGL(k_og_reorg_keys, grd, blk, 0, v->stream, og, n, g->d_flags, cur, clean,
                        (unsigned long long*)kb, (unsigned long long*)cnt);
@@ -525,6 +530,19 @@ int dmf_ogrid_get_dims(const dmf_ogrid* g, int32_t* dims) {
   return DMF_OK;
 }
 
+int dmf_ogrid_reorg_rounds(const dmf_ogrid* g, int32_t* rounds) {
+  if (!g || !rounds) return fail(DMF_ERR_INVALID, "null argument");
+  *rounds = g->reorg_rounds;
+  return DMF_OK;
+}
+
+int dmf_ogrid_set_reorg_round_cap(dmf_ogrid* g, int32_t cap) {
+  if (!g) return fail(DMF_ERR_INVALID, "null grid");
+  if (cap < 0 || cap > 65536) return fail(DMF_ERR_RANGE, "round cap must be 0 (default) or in [1, 65536]");
+  g->round_cap = cap;
+  return DMF_OK;
+}
+
 int dmf_ogrid_update_states_device(dmf_ogrid* g, const float* d_cloud, int64_t n_cloud, const float* d_normals,
                                    int64_t n_normals) {
   DMF_API_BEGIN
@@ -599,7 +617,9 @@ int dmf_ogrid_download(dmf_ogrid* g, int32_t mode, float* out, int64_t cap, int6
   OgS* F = nullptr;
   if (mode >= 2) {
     uint8_t* occ;
-    DMF_TRY(og_reorganize(g, mode == 3, &F, &occ, nullptr));
+    int rounds = 0;
+    DMF_TRY(og_reorganize(g, mode == 3, &F, &occ, &rounds));
+    g->reorg_rounds = rounds;
     hipLaunchKernelGGL(k_og_select_reorg, grd, dim3(256), 0, v->stream, occ, nc, (int32_t*)sel);
   } else {
     hipLaunchKernelGGL(k_og_select, grd, dim3(256), 0, v->stream, g->d_flags, g->d_count, nc, mode, (int32_t*)sel);

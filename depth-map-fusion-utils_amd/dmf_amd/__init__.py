@@ -686,6 +686,18 @@ class OccupancyGrid:
         x-major order; occupied reorganized voxels, x-major."""
         return self._download(3 if clean else 2)
 
+    @property
+    def reorg_rounds(self):
+        """dmf_ogrid_reorg_rounds (include/dmf_diag.h): rounds of the latest
+        downloadReorganizedCloud's fixed point, -1 = the serial fallback, 0 = none yet."""
+        r = C.c_int32()
+        check(self._L.dmf_ogrid_reorg_rounds(self._h, C.addressof(r)))
+        return r.value
+
+    def set_reorg_round_cap(self, cap):
+        """dmf_ogrid_set_reorg_round_cap: 0 = the default (64), else 1..65536; never changes a result."""
+        check(self._L.dmf_ogrid_set_reorg_round_cap(self._h, int(cap)))
+
     def set_state(self, normal, centroid, count, flags):
         """Write the dense voxels_ fields (normal, centroid (n, 3) float; count int32;
         flags occupied | normal_found << 1) — the reference's public state."""

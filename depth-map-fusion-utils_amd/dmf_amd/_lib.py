@@ -171,6 +171,8 @@ SIGNATURES = {
     "dmf_ogrid_state": (C.c_int, [_vp, _p, _p, _p, _p]),
     "dmf_ogrid_download": (C.c_int, [_vp, _i32, _p, _i64, _p]),
     "dmf_ogrid_set_state": (C.c_int, [_vp, _p, _p, _p, _p]),
+    "dmf_ogrid_reorg_rounds": (C.c_int, [_vp, _p]),
+    "dmf_ogrid_set_reorg_round_cap": (C.c_int, [_vp, _i32]),
     "dmf_device_malloc": (C.c_int, [_vp, _p, C.c_size_t]),
     "dmf_device_free": (C.c_int, [_vp, _vp]),
     "dmf_memcpy_h2d": (C.c_int, [_vp, _vp, _p, C.c_size_t]),

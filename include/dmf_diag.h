@@ -66,6 +66,16 @@ enum dmf_knob {
 int dmf_volume_set_knob(dmf_volume* v, int32_t knob, int64_t value);
 int dmf_volume_get_knob(const dmf_volume* v, int32_t knob, int64_t* value);
 
+/* OccupancyGrid: downloadReorganizedCloud (modes 2 / 3 of dmf_ogrid_download) iterates fixed-point
+ * rounds and, when they do not settle within the cap, runs the sequential loop on one lane; both
+ * give the same cloud.  rounds: the rounds the grid's latest mode-2/3 download ran until its fixed
+ * point settled (the confirming round counted), -1 when the serial fallback produced the result,
+ * 0 before any such download. */
+int dmf_ogrid_reorg_rounds(const dmf_ogrid* g, int32_t* rounds);
+/* Cap of the rounds, PER GRID, kept across dmf_ogrid_setup: 0 = the default (64), else 1..65536
+ * (DMF_ERR_RANGE otherwise). */
+int dmf_ogrid_set_reorg_round_cap(dmf_ogrid* g, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

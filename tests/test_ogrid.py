@@ -47,7 +47,8 @@ def test_ogrid_parity(oracle, k):
         gg.updateStates(cloud[part], normals[part])
     for a, b in zip(og.state(), gg.state()):
         assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
-    assert np.array_equal(og.download(0), gg.downloadCloud())
+    assert np.array_equal(og.download(0), gg.downloadCloud()) and len(og.download(0)) > 500
+    # no voxel of this input has more than 100 points: 0 rows (tests/test_ogrid_paths.py has the dense input)
     assert np.array_equal(og.download(1), gg.downloadHQCloud())
 
 
@@ -130,7 +131,7 @@ def test_reorganized_gpu_adversarial(oracle, grid, clean):
         gg.set_state(*st)
         exp = og.downloadReorganizedCloud(clean)
         got = gg.downloadReorganizedCloud(clean)
-        assert got.shape == exp.shape
+        assert got.shape == exp.shape and got.shape[0] > 10
         assert np.array_equal(got.view(np.uint32), exp.view(np.uint32))
 
 
