@@ -163,6 +163,45 @@ class RayTracingEngine {
                                   depth.data(), h.data()));
     cells.assign(h.begin(), h.end());
   }
+  // Extension: view gain over a fused log-odds grid -- per candidate pose the
+  // number of unknown cells (neither L >= occ nor L <= free) that its pixels' probe rays of depth
+  // range_mm reach before their first solid cell.  gain is resized to P; seen (may be null) to
+  // P * words uint64 in the mask layout of include/dmf.h (dmf_view_gain_words, dmf_view_mask_index).
+  // dmf_view_gain in include/dmf.h.
+  void viewGain(VoxelVolume& volume, const std::vector<int16_t>& logodds, const std::vector<Eigen::Affine3f>& poses,
+                int occ, int free, int range_mm, std::vector<unsigned long long int>& gain,
+                std::vector<unsigned long long int>* seen = nullptr) {
+    const size_t P = poses.size();
+    const size_t n = (size_t)volume.xdim_ * volume.ydim_ * volume.zdim_;
+    if (logodds.size() != n) throw std::invalid_argument("viewGain: logodds must hold xdim*ydim*zdim cells");
+    std::vector<float> p(12 * P);
+    for (size_t i = 0; i < P; ++i) dmf_compat::pose12(poses[i], &p[12 * i]);
+    int64_t words = 0;
+    dmf_check(dmf_view_gain_words(volume.handle(), &words));
+    std::vector<uint64_t> g(P, 0), m(seen ? P * (size_t)words : 0, 0);
+    const dmf_camera c = cam_.abi();
+    dmf_check(dmf_view_gain(volume.handle(), &c, logodds.data(), p.data(), (int32_t)P, occ, free, range_mm,
+                            seen ? m.data() : nullptr, g.data()));
+    gain.assign(g.begin(), g.end());
+    if (seen) seen->assign(m.begin(), m.end());
+  }
+  // Extension: greedySetCover (Algorithms.hpp:38-86) over those sets -- the
+  // indices of the poses to take next, in selection order.  dmf_next_best_views in include/dmf.h.
+  std::vector<int> nextBestViews(VoxelVolume& volume, const std::vector<int16_t>& logodds,
+                                 const std::vector<Eigen::Affine3f>& poses, int occ, int free, int range_mm,
+                                 int min_gain = 5) {
+    const size_t P = poses.size();
+    const size_t n = (size_t)volume.xdim_ * volume.ydim_ * volume.zdim_;
+    if (logodds.size() != n) throw std::invalid_argument("nextBestViews: logodds must hold xdim*ydim*zdim cells");
+    std::vector<float> p(12 * P);
+    for (size_t i = 0; i < P; ++i) dmf_compat::pose12(poses[i], &p[12 * i]);
+    std::vector<int32_t> sel(P ? P : 1, -1);
+    int32_t nsel = 0;
+    const dmf_camera c = cam_.abi();
+    dmf_check(dmf_next_best_views(volume.handle(), &c, logodds.data(), p.data(), (int32_t)P, occ, free, range_mm,
+                                  min_gain, sel.data(), &nsel, nullptr));
+    return std::vector<int>(sel.begin(), sel.begin() + nsel);
+  }
 
   // RayTracingEngine.hpp:229-264
   int rayTraceAndGetMinimum(VoxelVolume& volume, Eigen::Affine3f& T, int zdelta = 1, bool sparse = true) {

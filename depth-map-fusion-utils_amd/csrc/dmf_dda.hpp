@@ -1,7 +1,8 @@
 // dmf_dda.hpp — the exact integer 3D-DDA of a probe ray and the tiled counter
 // layout, shared by the fusion kernels (dmf_fuse.hip), the log-odds ray-cast (dmf_raycast.hip)
 // and the segment clearance (dmf_distance.hip): clip and quantise origin -> endpoint, the int32
-// walk state, one selection step, the walk in scalars, and the per-pixel ray of a depth frame.
+// walk state, one selection step, the walk in scalars, the per-pixel ray of a depth frame, and the
+// exact jump out of an aligned cube of cells (rc_jump: the ray-cast's and the view gain's).
 #pragma once
 #include "dmf_internal.hpp"
 
@@ -251,6 +252,68 @@ __device__ inline bool pixel_quant_go(const Geom& g, const CamP& cam, int d, con
 
 __device__ inline int pixel_depth(const CamP& cam, const uint16_t* __restrict__ depth, int p, int r, int c) {
   return (r >= cam.H || c >= cam.W) ? -1 : (int)depth[((int64_t)p * cam.H + r) * cam.W + c];
+}
+
+// floor(x / k) for 0 <= x < 2^35, 1 <= k < 2^29 with quotient < 2^12: a float estimate (within 1 of
+// the quotient: three roundings of 2^-24 relative each) and exact integer correction.
+__device__ inline int32_t rc_div(int64_t x, int32_t k) {
+  int32_t q = (int32_t)((float)x * __builtin_amdgcn_rcpf((float)k));
+  int64_t r = x - (int64_t)q * k;
+  if (r < 0) { --q; r += k; }
+  if (r < 0) { --q; r += k; }
+  if (r >= k) { ++q; r -= k; }
+  if (r >= k) { ++q; }
+  return q;
+}
+
+// Exact jump out of the aligned cube of (m + 1)^3 cells (m = 7 or 31) that holds the current cell:
+// the walk state after the crossing that leaves the cube, and the number of steps that takes.
+// In the cube, axis a can still make r_a crossings; its (r_a + 1)-th leaves.  The earliest of the
+// three leaving events in the walk's own order (crossing time, ties x < y < z) is found as
+// dda_select finds the next crossing, from F_ab = E_ab + r_a K_b - r_b K_a (the crossing-time
+// difference of the two leaving events); every crossing of another axis b that
+// precedes that event (a*, r*) in the same order is taken with it: #{k >= 0 : k K_a* < X} for
+// b > a*, <= X for b < a*, X = (h_a* + 2Q r*) |dq_b| - h_b |dq_a*| = +-E + r* K_b.  A step along a
+// adds K_b to E_ab and takes K_a from E_ba, so n_a steps per axis move E_ab by n_a K_b - n_b K_a.
+// A non-moving axis has K = 0, r = 0 and |E| = kNever against a moving one: it neither leaves
+// nor steps.  Returns the steps; more than the ray has left means the ray ends in the cube.
+__device__ inline int rc_jump(int m, Walk& W) {
+  const int r0 = W.st0 > 0 ? m - (W.c0 & m) : (W.st0 < 0 ? (W.c0 & m) : 0);
+  const int r1 = W.st1 > 0 ? m - (W.c1 & m) : (W.st1 < 0 ? (W.c1 & m) : 0);
+  const int r2 = W.st2 > 0 ? m - (W.c2 & m) : (W.st2 < 0 ? (W.c2 & m) : 0);
+  const int64_t F01 = (int64_t)W.E01 + (int64_t)r0 * W.K1 - (int64_t)r1 * W.K0;
+  const int64_t F02 = (int64_t)W.E02 + (int64_t)r0 * W.K2 - (int64_t)r2 * W.K0;
+  const int64_t F12 = (int64_t)W.E12 + (int64_t)r1 * W.K2 - (int64_t)r2 * W.K1;
+  const bool b10 = F01 > 0;
+  const bool s2 = (b10 ? F12 : F02) > 0, s1 = !s2 && b10;
+  // crossings of axis b before the leaving event of a*: d = h_a* |dq_b| - h_b |dq_a*|
+  auto before = [](int64_t d, int rs, int32_t kb, int32_t ka, bool b_after) -> int {
+    const int64_t x = d + (int64_t)rs * kb;
+    if (x < 0 || ka == 0) return 0;
+    const int32_t q = rc_div(x, ka);
+    return b_after ? (int)(q + ((int64_t)q * ka < x ? 1 : 0)) : (int)q + 1;
+  };
+  int n0, n1, n2;
+  if (s2) {
+    n2 = r2 + 1;
+    n0 = before(-(int64_t)W.E02, r2, W.K0, W.K2, false);
+    n1 = before(-(int64_t)W.E12, r2, W.K1, W.K2, false);
+  } else if (s1) {
+    n1 = r1 + 1;
+    n0 = before(-(int64_t)W.E01, r1, W.K0, W.K1, false);
+    n2 = before((int64_t)W.E12, r1, W.K2, W.K1, true);
+  } else {
+    n0 = r0 + 1;
+    n1 = before((int64_t)W.E01, r0, W.K1, W.K0, true);
+    n2 = before((int64_t)W.E02, r0, W.K2, W.K0, true);
+  }
+  W.c0 += W.st0 * n0;
+  W.c1 += W.st1 * n1;
+  W.c2 += W.st2 * n2;
+  W.E01 = (int32_t)((uint32_t)W.E01 + (uint32_t)n0 * (uint32_t)W.K1 - (uint32_t)n1 * (uint32_t)W.K0);
+  W.E02 = (int32_t)((uint32_t)W.E02 + (uint32_t)n0 * (uint32_t)W.K2 - (uint32_t)n2 * (uint32_t)W.K0);
+  W.E12 = (int32_t)((uint32_t)W.E12 + (uint32_t)n1 * (uint32_t)W.K2 - (uint32_t)n2 * (uint32_t)W.K1);
+  return n0 + n1 + n2;
 }
 
 }  // namespace dmf

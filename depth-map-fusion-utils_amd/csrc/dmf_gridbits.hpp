@@ -97,4 +97,25 @@ __device__ inline void tile_mask_pass(const Geom& g, const GridTiles& tl, const 
   }
 }
 
+// One word of the brick level over a tile level: lane k < 32 of a 64-lane workgroup ORs the 4x4x4
+// tile bits of brick 32 * block + k (tiles past the grid's last tile row are absent); every lane
+// returns the word.
+__device__ inline uint32_t brick_word(const GridTiles& tl, const uint32_t* __restrict__ coarse) {
+  const uint32_t b = blockIdx.x * 32u + (threadIdx.x & 31u);
+  bool any = false;
+  if (threadIdx.x < 32 && b < tl.nbricks) {
+    const uint32_t bz = b % tl.nbz, r = b / tl.nbz, by = r % tl.nby, bx = r / tl.nby;
+    for (uint32_t dx = 0; dx < 4; ++dx)
+      for (uint32_t dy = 0; dy < 4; ++dy) {
+        const uint32_t tx = bx * 4 + dx, ty = by * 4 + dy;
+        if (tx >= tl.ntx || ty >= tl.nty) continue;
+        for (uint32_t tz = bz * 4; tz < bz * 4 + 4 && tz < tl.ntz; ++tz) {
+          const uint32_t t = (tx * tl.nty + ty) * tl.ntz + tz;
+          any |= (coarse[t >> 5] >> (t & 31u)) & 1u;
+        }
+      }
+  }
+  return (uint32_t)__builtin_amdgcn_ballot_w64(any);
+}
+
 }  // namespace dmf

@@ -74,6 +74,9 @@ enum ScratchSlot {
   kScSfSolid, kScSfFree, kScSfSurf, kScSfCounts, kScSfBases, kScSfTotals, kScSfHash, kScSfXyz, kScSfNrm,
   // the distance field (dmf_distance.hip): the y / x passes' envelope stacks, and the host forms' field
   kScDfStack, kScDfDist,
+  // view gain (dmf_viewgain.hip): the solid and unknown masks, their tile + brick levels, and the
+  // masks and gains of the calls that keep them in scratch
+  kScVgSolid, kScVgUnknown, kScVgCoarse, kScVgSeen, kScVgGain,
   // brick-owned fusion (dmf_fuse.hip): one block, buffer b of staging slot s at bk_key(b, s)
   kScBkFirst, kScBkEnd = kScBkFirst + 2 * kBkBufCount
 };
@@ -138,5 +141,14 @@ int sort_pairs_u32(dmf_volume* v, uint32_t* keys, uint32_t* vals, size_t n, int 
 int compact_masks(dmf_volume* v, const uint64_t* d_masks, int P, int64_t words, int64_t nelem,
                   int64_t* counts_h, uint64_t** d_out_lists, int64_t* total, int value_kind);
 enum { kValueSlotHash = 0, kValueEnumCentroidHash = 1 };
+
+// greedySetCover (Algorithms.hpp:38-86) over P device bitmasks of `words` uint64 (dmf_trace.hip);
+// the selection order comes back on the host.  Scratch: kScTmp and kScCount.
+int greedy_cover(dmf_volume* v, const uint64_t* d_masks, int P, int64_t words, int min_gain, int32_t* selected,
+                 int32_t* nselected);
+// The log-odds ray-cast's argument checks (dmf_raycast.hip): the plain arguments without access to
+// the volume, then check_fuse_call.
+int check_raycast(const dmf_volume* v, const dmf_camera* cam, const void* logodds, const void* poses, int32_t P,
+                  int32_t range_mm);
 
 }  // namespace dmf

@@ -9,7 +9,7 @@
 //  k_rc_cast   — one lane per pixel: dda_setup once, then the walk of dmf_dda.hpp.  The tile bit is
 //                read when the tile changes, a mask word only inside a non-empty tile and only
 //                when the word changes.  <true> also reads the brick bit when the brick changes and
-//                leaves a wholly empty brick or tile in one exact jump (rc_jump) instead of cell by
+//                leaves a wholly empty brick or tile in one exact jump (rc_jump, dmf_dda.hpp) instead of cell by
 //                cell.  Skipping removes loads and tests of empty cells, never cells of the
 //                sequence: the reported cell is the plain walk's.
 #include "dmf_dda.hpp"
@@ -44,88 +44,11 @@ __global__ __launch_bounds__(kMaskThreads) void k_rc_mask(Geom g, GridTiles tl, 
   }
 }
 
-// One lane per brick: the OR of its 4x4x4 tile bits (tiles past the grid's last tile row are
-// absent).  One workgroup per 32 bricks = one word of the brick level.
+// One workgroup per 32 bricks = one word of the brick level (brick_word, dmf_gridbits.hpp).
 __global__ __launch_bounds__(64) void k_rc_bricks(GridTiles tl, const uint32_t* __restrict__ coarse,
                                                   uint32_t* __restrict__ bricks) {
-  const uint32_t b = blockIdx.x * 32u + (threadIdx.x & 31u);
-  bool any = false;
-  if (threadIdx.x < 32 && b < tl.nbricks) {
-    const uint32_t bz = b % tl.nbz, r = b / tl.nbz, by = r % tl.nby, bx = r / tl.nby;
-    for (uint32_t dx = 0; dx < 4; ++dx)
-      for (uint32_t dy = 0; dy < 4; ++dy) {
-        const uint32_t tx = bx * 4 + dx, ty = by * 4 + dy;
-        if (tx >= tl.ntx || ty >= tl.nty) continue;
-        for (uint32_t tz = bz * 4; tz < bz * 4 + 4 && tz < tl.ntz; ++tz) {
-          const uint32_t t = (tx * tl.nty + ty) * tl.ntz + tz;
-          any |= (coarse[t >> 5] >> (t & 31u)) & 1u;
-        }
-      }
-  }
-  const uint64_t m = __builtin_amdgcn_ballot_w64(any);
-  if (threadIdx.x == 0) bricks[blockIdx.x] = (uint32_t)m;
-}
-
-// floor(x / k) for 0 <= x < 2^35, 1 <= k < 2^29 with quotient < 2^12: a float estimate (within 1 of
-// the quotient: three roundings of 2^-24 relative each) and exact integer correction.
-__device__ inline int32_t rc_div(int64_t x, int32_t k) {
-  int32_t q = (int32_t)((float)x * __builtin_amdgcn_rcpf((float)k));
-  int64_t r = x - (int64_t)q * k;
-  if (r < 0) { --q; r += k; }
-  if (r < 0) { --q; r += k; }
-  if (r >= k) { ++q; r -= k; }
-  if (r >= k) { ++q; }
-  return q;
-}
-
-// Exact jump out of the aligned cube of (m + 1)^3 cells (m = 7 or 31) that holds the current cell:
-// the walk state after the crossing that leaves the cube, and the number of steps that takes.
-// In the cube, axis a can still make r_a crossings; its (r_a + 1)-th leaves.  The earliest of the
-// three leaving events in the walk's own order (crossing time, ties x < y < z) is found as
-// dda_select finds the next crossing, from F_ab = E_ab + r_a K_b - r_b K_a (the crossing-time
-// difference of the two leaving events); every crossing of another axis b that
-// precedes that event (a*, r*) in the same order is taken with it: #{k >= 0 : k K_a* < X} for
-// b > a*, <= X for b < a*, X = (h_a* + 2Q r*) |dq_b| - h_b |dq_a*| = +-E + r* K_b.  A step along a
-// adds K_b to E_ab and takes K_a from E_ba, so n_a steps per axis move E_ab by n_a K_b - n_b K_a.
-// A non-moving axis has K = 0, r = 0 and |E| = kNever against a moving one: it neither leaves
-// nor steps.  Returns the steps; more than the ray has left means the ray ends in the cube.
-__device__ inline int rc_jump(int m, Walk& W) {
-  const int r0 = W.st0 > 0 ? m - (W.c0 & m) : (W.st0 < 0 ? (W.c0 & m) : 0);
-  const int r1 = W.st1 > 0 ? m - (W.c1 & m) : (W.st1 < 0 ? (W.c1 & m) : 0);
-  const int r2 = W.st2 > 0 ? m - (W.c2 & m) : (W.st2 < 0 ? (W.c2 & m) : 0);
-  const int64_t F01 = (int64_t)W.E01 + (int64_t)r0 * W.K1 - (int64_t)r1 * W.K0;
-  const int64_t F02 = (int64_t)W.E02 + (int64_t)r0 * W.K2 - (int64_t)r2 * W.K0;
-  const int64_t F12 = (int64_t)W.E12 + (int64_t)r1 * W.K2 - (int64_t)r2 * W.K1;
-  const bool b10 = F01 > 0;
-  const bool s2 = (b10 ? F12 : F02) > 0, s1 = !s2 && b10;
-  // crossings of axis b before the leaving event of a*: d = h_a* |dq_b| - h_b |dq_a*|
-  auto before = [](int64_t d, int rs, int32_t kb, int32_t ka, bool b_after) -> int {
-    const int64_t x = d + (int64_t)rs * kb;
-    if (x < 0 || ka == 0) return 0;
-    const int32_t q = rc_div(x, ka);
-    return b_after ? (int)(q + ((int64_t)q * ka < x ? 1 : 0)) : (int)q + 1;
-  };
-  int n0, n1, n2;
-  if (s2) {
-    n2 = r2 + 1;
-    n0 = before(-(int64_t)W.E02, r2, W.K0, W.K2, false);
-    n1 = before(-(int64_t)W.E12, r2, W.K1, W.K2, false);
-  } else if (s1) {
-    n1 = r1 + 1;
-    n0 = before(-(int64_t)W.E01, r1, W.K0, W.K1, false);
-    n2 = before((int64_t)W.E12, r1, W.K2, W.K1, true);
-  } else {
-    n0 = r0 + 1;
-    n1 = before((int64_t)W.E01, r0, W.K1, W.K0, true);
-    n2 = before((int64_t)W.E02, r0, W.K2, W.K0, true);
-  }
-  W.c0 += W.st0 * n0;
-  W.c1 += W.st1 * n1;
-  W.c2 += W.st2 * n2;
-  W.E01 = (int32_t)((uint32_t)W.E01 + (uint32_t)n0 * (uint32_t)W.K1 - (uint32_t)n1 * (uint32_t)W.K0);
-  W.E02 = (int32_t)((uint32_t)W.E02 + (uint32_t)n0 * (uint32_t)W.K2 - (uint32_t)n2 * (uint32_t)W.K0);
-  W.E12 = (int32_t)((uint32_t)W.E12 + (uint32_t)n1 * (uint32_t)W.K2 - (uint32_t)n2 * (uint32_t)W.K1);
-  return n0 + n1 + n2;
+  const uint32_t m = brick_word(tl, coarse);
+  if (threadIdx.x == 0) bricks[blockIdx.x] = m;
 }
 
 // One 64-lane workgroup per 8x8 pixel packet of one pose (neighbouring rays share tiles and
@@ -220,8 +143,8 @@ __global__ __launch_bounds__(64) void k_rc_cast(Geom g, GridTiles tl, CamP cam, 
 
 // The plain arguments first (no access to the volume: they are rejected without a device), then
 // what the fusion checks (constructed, camera, P in 1..65535, grid size).
-static int check_raycast(const dmf_volume* v, const dmf_camera* cam, const void* logodds, const void* poses, int32_t P,
-                         int32_t range_mm) {
+int check_raycast(const dmf_volume* v, const dmf_camera* cam, const void* logodds, const void* poses, int32_t P,
+                  int32_t range_mm) {
   if (!v || !cam || !logodds || !poses) return fail(DMF_ERR_INVALID, "null argument");
   if (range_mm < 1 || range_mm > 65535) return fail(DMF_ERR_INVALID, "range_mm %d out of range [1,65535]", range_mm);
   if (P < 0) return fail(DMF_ERR_INVALID, "negative pose count %d", P);

@@ -716,8 +716,8 @@ __global__ __launch_bounds__(256) void k_cover_merge(const uint64_t* __restrict_
   if (w < words) covered[w] |= masks[(int64_t)ctl->sel * words + w];
 }
 
-static int greedy_cover(dmf_volume* v, const uint64_t* d_masks, int P, int64_t words, int min_gain,
-                        int32_t* selected, int32_t* nselected) {
+int greedy_cover(dmf_volume* v, const uint64_t* d_masks, int P, int64_t words, int min_gain, int32_t* selected,
+                 int32_t* nselected) {
   if (P <= 0) { *nselected = 0; return DMF_OK; }
   void *cov, *aux;
   const size_t cov_bytes = sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1);

@@ -115,6 +115,19 @@ class Camera:
         return np.float32(np.sqrt((x1 - x2) ** 2 + (y1 - y2) ** 2))
 
 
+def _unpack_view_mask(mask, dims):
+    """VoxelVolume.view_mask_dense over explicit grid dimensions (numpy only)."""
+    nx, ny, nz = (int(d) for d in dims)
+    tx, ty, tz = (nx + 7) // 8, (ny + 7) // 8, (nz + 7) // 8
+    m = np.ascontiguousarray(mask, np.uint64).reshape(-1)
+    if m.size != 8 * tx * ty * tz:
+        raise ValueError(f"mask must hold {8 * tx * ty * tz} uint64 words, got {m.size}")
+    bits = np.unpackbits(m.astype("<u8").view(np.uint8), bitorder="little").astype(bool)
+    # (tile x, tile y, tile z, x & 7, y & 7, z & 7) -> (x, y, z)
+    cells = bits.reshape(tx, ty, tz, 8, 8, 8).transpose(0, 3, 1, 4, 2, 5).reshape(tx * 8, ty * 8, tz * 8)
+    return np.ascontiguousarray(cells[:nx, :ny, :nz])
+
+
 class VoxelVolume:
     """Volume.hpp:50-255 VoxelVolume, device-resident (flat occupancy bitmask,
     dense slot map, occupied_cells_ list, CSR per-voxel points/normals)."""
@@ -180,6 +193,20 @@ class VoxelVolume:
     def dims(self):
         i = self.info()
         return i["xdim"], i["ydim"], i["zdim"]
+
+    # -- view-gain masks
+    def view_gain_words(self):
+        """uint64 words of one pose's view mask (dmf_view_gain_words)."""
+        w = C.c_int64(0)
+        check(self._L.dmf_view_gain_words(self._h, C.addressof(w)))
+        return w.value
+
+    def view_mask_dense(self, mask):
+        """One pose's view mask (words uint64, RayTracingEngine.view_gain(masks=True)) -> bool
+        (xdim, ydim, zdim).  Layout: cell (x, y, z) is bit i & 63 of word i >> 6 with
+        i = tile << 9 | (x & 7) << 6 | (y & 7) << 3 | (z & 7), 8x8x8-cell tiles x-major over the
+        grid padded to whole tiles."""
+        return _unpack_view_mask(mask, self.dims)
 
     # -- hashing helpers (Volume.hpp:135-170, 230-233): host formulas
     def getHashId(self, x, y, z):
@@ -584,6 +611,43 @@ class RayTracingEngine:
         check(volume._L.dmf_raycast_logodds(volume._h, self._c(), ptr(lo), ptr(poses), P, int(threshold),
                                             int(range_mm), ptr(depth), ptr(cell)))
         return depth, cell
+
+    # view gain over a fused log-odds grid and next-best-view selection
+    @staticmethod
+    def _grid_and_poses(volume, logodds, poses):
+        poses = _poses(poses)
+        n = int(np.prod(volume.dims))
+        lo = np.asarray(logodds)
+        if lo.dtype != np.int16 or lo.size != n:
+            raise ValueError(f"logodds must be int16 with {n} cells (x-major over dims {tuple(volume.dims)}), "
+                             f"got {lo.dtype} with {lo.size}")
+        return np.ascontiguousarray(lo).reshape(-1), poses
+
+    def view_gain(self, volume, logodds, poses, occ_threshold=1, free_threshold=-1, range_mm=1000, masks=False):
+        """How many unobserved cells each candidate pose would see in the int16 log-odds grid
+        `logodds` (as fuse_finalize returns it): -> gain (P,) uint64, and with masks=True also
+        seen (P, words) uint64 (VoxelVolume.view_mask_dense unpacks one row).  A cell is solid iff
+        L >= occ_threshold, free iff not solid and L <= free_threshold, unknown otherwise; a
+        pixel sees the cells of its probe ray (depth range_mm) before the first solid one."""
+        lo, poses = self._grid_and_poses(volume, logodds, poses)
+        P = poses.shape[0]
+        gain = np.zeros(P, np.uint64)
+        seen = np.zeros((P, volume.view_gain_words()), np.uint64) if masks else None
+        check(volume._L.dmf_view_gain(volume._h, self._c(), ptr(lo), ptr(poses), P, int(occ_threshold),
+                                      int(free_threshold), int(range_mm), ptr(seen) if masks else None, ptr(gain)))
+        return (gain, seen) if masks else gain
+
+    def next_best_views(self, volume, logodds, poses, occ_threshold=1, free_threshold=-1, range_mm=1000, min_gain=5):
+        """greedySetCover over the poses' sets of unobserved visible cells (view_gain's masks):
+        -> (selected pose indices in selection order (int32), gain (P,) uint64: each pose's own
+        gain).  The selection stops when the best pose adds nothing or fewer than min_gain cells."""
+        lo, poses = self._grid_and_poses(volume, logodds, poses)
+        P = poses.shape[0]
+        sel, nsel, gain = np.zeros(max(P, 1), np.int32), C.c_int32(0), np.zeros(P, np.uint64)
+        check(volume._L.dmf_next_best_views(volume._h, self._c(), ptr(lo), ptr(poses), P, int(occ_threshold),
+                                            int(free_threshold), int(range_mm), int(min_gain), ptr(sel),
+                                            C.addressof(nsel), ptr(gain)))
+        return sel[:nsel.value].copy(), gain
 
 
 def will_collide(volume, a, b):

@@ -131,6 +131,12 @@ SIGNATURES = {
     "dmf_fuse_finalize_device": (C.c_int, [_vp, _p, _p, _p, _p]),
     "dmf_raycast_logodds": (C.c_int, [_vp, _p, _p, _p, _i32, _i32, _i32, _p, _p]),
     "dmf_raycast_logodds_device": (C.c_int, [_vp, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
+    "dmf_view_gain_words": (C.c_int, [_vp, _p]),
+    "dmf_view_mask_index": (C.c_int, [_vp, _i32, _i32, _i32, _p]),
+    "dmf_view_gain": (C.c_int, [_vp, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "dmf_view_gain_device": (C.c_int, [_vp, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
+    "dmf_next_best_views": (C.c_int, [_vp, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p]),
+    "dmf_next_best_views_device": (C.c_int, [_vp, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p]),
     "dmf_grid_surface_device": (C.c_int, [_vp, _p, _i32, _i32, _p, _p, _p, _i64, _p]),
     "dmf_grid_surface": (C.c_int, [_vp, _p, _i32, _i32, _p, _p, _p, _i64, _p, _p]),
     "dmf_volume_integrate_surface": (C.c_int, [_vp, _p, _i32, _i32, _p]),
@@ -233,7 +239,7 @@ def declared_symbols():
 FUSE_DEFAULT, FUSE_LDS_BOX, FUSE_CELL_WALK, FUSE_SLAB = 0, 31, 40, 57
 KNOBS = {"super_poses": 1, "pair_cap": 2, "batch_poses": 3, "part_max": 4, "span": 5, "tail_split": 6,
          "reverse_kernel": 7, "fwd_skip": 8, "a_hash": 9, "fault_inject": 10, "fwd_kernel": 11,
-         "bdist_cap": 12, "raycast_walk": 13}
+         "bdist_cap": 12, "raycast_walk": 13, "viewgain_walk": 14, "viewgain_batch": 15}
 
 
 def fuse_status(vol):

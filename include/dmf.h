@@ -379,6 +379,54 @@ int dmf_raycast_logodds_device(dmf_volume* v, const dmf_camera* cam, const int16
                                const float* d_poses, int32_t P, int32_t threshold, int32_t range_mm,
                                int32_t* d_depth, uint64_t* d_cell, uint64_t* d_stats);
 
+/* View gain over a fused log-odds grid and next-best-view selection: which cells
+ * that have not been observed yet would a camera at each of P candidate poses see?  `logodds` is
+ * the int16 grid, x-major, as dmf_fuse_finalize* writes it.  A cell is solid iff its log-odds >=
+ * occ_threshold, free iff it is not solid and its log-odds <= free_threshold, unknown otherwise
+ * (any int32 pair; with (1, -1) unknown is exactly log-odds 0).  Pixel (r, c) of pose p walks the
+ * ray-cast's cell sequence (§4.1: the fusion's ray for depth range_mm, 1..65535) and sees the
+ * cells strictly before its first solid cell.  seen[p] = the unknown cells seen by at least one
+ * pixel; gain[p] = their number.  Only the volume's geometry is used; its point-cloud occupancy
+ * is neither read nor changed.
+ *
+ * Mask layout (§4.5): `words` = 8 x the grid's 8x8x8-cell tiles uint64 per pose; cell (x, y, z)
+ * is bit i & 63 of word i >> 6 with i = tile << 9 | (x & 7) << 6 | (y & 7) << 3 | (z & 7), tiles
+ * x-major over the grid padded to whole tiles; bits of padding cells are 0.  P x words uint64 is
+ * what dmf_greedy_set_cover_masks_device takes.  dmf_view_gain_words and dmf_view_mask_index
+ * (§4.5) are host arithmetic over the constructed volume's dimensions: the words per pose, and
+ * the bit index i of a cell (DMF_ERR_INVALID outside the grid). */
+int dmf_view_gain_words(const dmf_volume* v, int64_t* words);
+int dmf_view_mask_index(const dmf_volume* v, int32_t x, int32_t y, int32_t z, uint64_t* bit);
+/* §4.5, device form: device pointers, only enqueues on the volume's stream, allocates only when
+ * its scratch must grow.  d_seen (P x words, overwritten: the call zeroes it) and d_gain (P) may
+ * each be NULL, not both.  With d_seen NULL the masks live in the call's scratch, in pose batches
+ * of at most max(1, 256 MiB / bytes per pose) poses: counting many candidates never needs P
+ * masks.  d_stats (may be NULL): 3 counters += {rays with a non-empty sequence, rays stopped by
+ * a solid cell, unknown cells seen summed over rays (a cell counts once per ray that sees it)}.
+ * Status rules are the ray-cast's; all outputs NULL is DMF_ERR_INVALID; every argument is checked
+ * before the volume is touched. */
+int dmf_view_gain_device(dmf_volume* v, const dmf_camera* cam, const int16_t* d_logodds, const float* d_poses,
+                         int32_t P, int32_t occ_threshold, int32_t free_threshold, int32_t range_mm,
+                         uint64_t* d_seen, uint64_t* d_gain, uint64_t* d_stats);
+/* §4.5, host form: host pointers (seen: P x words, gain: P; each may be NULL, not both), uploads
+ * the grid and the poses, synchronises. */
+int dmf_view_gain(dmf_volume* v, const dmf_camera* cam, const int16_t* logodds, const float* poses, int32_t P,
+                  int32_t occ_threshold, int32_t free_threshold, int32_t range_mm, uint64_t* seen, uint64_t* gain);
+/* §4.5, next best views: greedySetCover (Algorithms.hpp:38-86) over the P sets seen[p], as
+ * dmf_greedy_set_cover_masks_device does it: the pose that adds most cells not yet covered, ties
+ * to the lowest index, until the best adds nothing or fewer than min_gain.  The masks of all P
+ * poses stay in device scratch (an allocation that fails: DMF_ERR_NOMEM); selected[P] receives
+ * the chosen pose indices in selection order and *nselected their number, on the host; gain
+ * (host, P, may be NULL) each pose's own gain[p].  Synchronises.  The device form takes a device
+ * grid and device poses, the host form host ones. */
+int dmf_next_best_views_device(dmf_volume* v, const dmf_camera* cam, const int16_t* d_logodds,
+                               const float* d_poses, int32_t P, int32_t occ_threshold, int32_t free_threshold,
+                               int32_t range_mm, int32_t min_gain, int32_t* selected, int32_t* nselected,
+                               uint64_t* gain);
+int dmf_next_best_views(dmf_volume* v, const dmf_camera* cam, const int16_t* logodds, const float* poses,
+                        int32_t P, int32_t occ_threshold, int32_t free_threshold, int32_t range_mm,
+                        int32_t min_gain, int32_t* selected, int32_t* nselected, uint64_t* gain);
+
 /* Surface of a fused log-odds grid as an oriented cloud, in order: the cloud
  * that integratePointCloud(cloud, normals) (Volume.hpp:199-228) takes, from `logodds` (int16,
  * x-major over xdim*ydim*zdim, as dmf_fuse_finalize* writes it).  A cell is solid iff its

@@ -61,7 +61,13 @@ enum dmf_knob {
   DMF_KNOB_RAYCAST_WALK = 13, /* log-odds ray-cast (dmf_raycast_logodds*): 0 default, 1 the masked cell-by-cell walk,
                                  2 the walk that jumps wholly empty 32^3 bricks and 8^3 tiles exactly; identical
                                  outputs */
-  DMF_KNOB_COUNT = 14
+  DMF_KNOB_VIEWGAIN_WALK = 14, /* view gain (dmf_view_gain*, dmf_next_best_views*): 0 default, 1 the plain walk (cell by
+                                  cell, one atomic OR per unknown visible cell), 2 the walk that jumps wholly free
+                                  bricks and tiles and issues one atomic OR per mask word, 3 as 2 but reads the word
+                                  first and skips an atomic that would add nothing; identical masks */
+  DMF_KNOB_VIEWGAIN_BATCH = 15, /* cap of the poses per internal batch of a dmf_view_gain_device call that keeps its
+                                   masks in scratch (d_seen NULL); 0 = the default, 256 MiB of masks */
+  DMF_KNOB_COUNT = 16
 };
 int dmf_volume_set_knob(dmf_volume* v, int32_t knob, int64_t value);
 int dmf_volume_get_knob(const dmf_volume* v, int32_t knob, int64_t* value);
