@@ -678,30 +678,37 @@ __global__ __launch_bounds__(256) void k_cover_gain(const uint64_t* __restrict__
   if (threadIdx.x == 0) gain[p] = part[0] + part[1] + part[2] + part[3];
 }
 
+// The pick's order: the larger gain, and among equal gains the smaller index.
+__device__ __forceinline__ bool cover_better(unsigned long long g, int p, unsigned long long bg, int bp) {
+  return g > bg || (g == bg && p < bp);
+}
+
 __global__ __launch_bounds__(256) void k_cover_pick(const unsigned long long* __restrict__ gain, int P, int min_gain,
                                                     uint8_t* __restrict__ removed, int32_t* __restrict__ selected,
                                                     CoverCtl* __restrict__ ctl) {
   if (ctl->done) return;
-  // argmax with ties to the smallest index: key = gain << 32 | (2^32 - 1 - p)
-  unsigned long long best = 0;
-  for (int p = threadIdx.x; p < P; p += blockDim.x) {
-    const unsigned long long k = (gain[p] << 32) | (unsigned long long)(0xffffffffu - (uint32_t)p);
-    best = k > best ? k : best;
-  }
+  // argmax with ties to the smallest index, over the pair (gain, index): the gain keeps all its
+  // 64 bits (up to 64 * words), so the two do not share one key
+  unsigned long long g = 0;
+  int p = P;
+  for (int q = threadIdx.x; q < P; q += blockDim.x)
+    if (cover_better(gain[q], q, g, p)) { g = gain[q]; p = q; }
   for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_down(best, o, 64);
-    best = t > best ? t : best;
+    const unsigned long long tg = __shfl_down(g, o, 64);
+    const int tp = __shfl_down(p, o, 64);
+    if (cover_better(tg, tp, g, p)) { g = tg; p = tp; }
   }
-  __shared__ unsigned long long part[4];
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = best;
+  __shared__ unsigned long long part_g[4];
+  __shared__ int part_p[4];
+  if ((threadIdx.x & 63) == 0) { part_g[threadIdx.x >> 6] = g; part_p[threadIdx.x >> 6] = p; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int i = 1; i < 4; ++i) best = part[i] > best ? part[i] : best;
-    const unsigned long long g = best >> 32;
-    if (g == 0 || g < (unsigned long long)min_gain) {  // selected == -1, or max_points < 5
+    for (int i = 1; i < 4; ++i)
+      if (cover_better(part_g[i], part_p[i], g, p)) { g = part_g[i]; p = part_p[i]; }
+    // selected == -1, or max_points < 5 (a signed compare: min_gain <= 0 stops at "adds nothing" alone)
+    if (g == 0 || (min_gain > 0 && g < (unsigned long long)min_gain)) {
       ctl->done = 1;
     } else {
-      const int p = (int)(0xffffffffu - (uint32_t)(best & 0xffffffffu));
       ctl->sel = p;
       selected[ctl->nsel++] = p;
       removed[p] = 1;

@@ -178,7 +178,8 @@ int dmf_reverse_ray_trace(dmf_volume* v, const dmf_camera* cam, const float* pos
 /* Set-cover consumer: Algorithms.hpp:38-86 greedySetCover over the reverseRayTraceFast
  * good sets of P candidate poses (the loop of tests/SetCover.cpp:218-240).  selected[P]
  * receives the chosen pose indices in selection order; the reference stops when no set
- * adds anything or the best adds fewer than min_gain (5) voxels. */
+ * adds anything or the best adds fewer than min_gain (5) voxels.  min_gain is signed:
+ * min_gain <= 0 means "until nothing is added". */
 int dmf_greedy_set_cover(dmf_volume* v, const dmf_camera* cam, const float* poses, int32_t P, int32_t min_gain,
                          int32_t* selected, int32_t* nselected);
 /* Same over caller bitmasks (P x words uint64, e.g. d_good of dmf_reverse_visibility_device). */

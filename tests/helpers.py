@@ -233,3 +233,14 @@ class DeviceCalls:
         self._lib.check(self.L.dmf_greedy_set_cover_masks_device(self.h, self.upload(masks), P, words, int(min_gain),
                                                                  sel.ctypes.data, C.addressof(n)))
         return sel[:n.value]
+
+    def cover_masks_guarded(self, d_masks, P, words, min_gain, fill=-7, guard=5):
+        """dmf_greedy_set_cover_masks_device over device masks with selected (P + guard entries) and
+        nselected pre-filled with `fill`, which never is an output -> (status, nselected, the whole
+        of selected): an entry the call left unwritten, or wrote past the end, shows."""
+        import ctypes as C
+        sel = np.full(max(int(P), 0) + guard, fill, np.int32)
+        n = C.c_int32(fill)
+        st = self.L.dmf_greedy_set_cover_masks_device(self.h, d_masks, int(P), int(words), int(min_gain),
+                                                      sel.ctypes.data, C.addressof(n))
+        return st, n.value, sel
