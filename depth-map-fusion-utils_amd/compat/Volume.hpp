@@ -8,6 +8,7 @@
 // lazily from the device whenever the device state changed (engine calls with viz
 // flags, integration).  Copying is disabled, as a copy of the reference double-frees.
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -172,6 +173,30 @@ class VoxelVolume {
     if (!a.empty())
       dmf_check(dmf_grid_clearance(h_, dist2.data(), pa.data(), pb.data(), (int64_t)a.size(), out.data()));
     return out;
+  }
+
+  // Travel field over a distance field (dmf_grid_travel; not in the reference):
+  // out[(x * ydim_ + y) * zdim_ + z] = the least number of face-to-face steps from any seed cell
+  // {x, y, z} through cells with dist2 >= radius2; DMF_NO_PATH where a cell is blocked or not
+  // reachable.  Returns {traversable cells, reached cells, largest finite hop count}.
+  std::array<uint64_t, 3> travelField(const std::vector<uint32_t>& dist2, uint32_t radius2,
+                                      const std::vector<std::array<int32_t, 3>>& seeds, std::vector<uint32_t>& out) {
+    if (dist2.size() != (size_t)xdim_ * ydim_ * zdim_) throw std::invalid_argument("travelField: field size");
+    out.assign(dist2.size(), 0);
+    std::array<uint64_t, 3> info{{0, 0, 0}};
+    dmf_check(dmf_grid_travel(h_, dist2.data(), radius2, seeds.empty() ? nullptr : seeds[0].data(),
+                              (int64_t)seeds.size(), out.data(), info.data()));
+    return info;
+  }
+  // The path target, ..., seed in a field of travelField (hops[target] + 1 cells, ties to the
+  // first of -x +x -y +y -z +z); empty for a target outside the grid or with DMF_NO_PATH.
+  std::vector<std::array<int32_t, 3>> pathTo(const std::vector<uint32_t>& hops, const std::array<int32_t, 3>& target) {
+    if (hops.size() != (size_t)xdim_ * ydim_ * zdim_) throw std::invalid_argument("pathTo: field size");
+    int64_t n = 0;
+    dmf_check(dmf_grid_path(h_, hops.data(), target.data(), nullptr, 0, &n));
+    std::vector<std::array<int32_t, 3>> cells((size_t)n);
+    if (n) dmf_check(dmf_grid_path(h_, hops.data(), target.data(), cells[0].data(), n, &n));
+    return cells;
   }
 
   // Volume.hpp:235-255 (with the reference's `i==j==k==0` test)

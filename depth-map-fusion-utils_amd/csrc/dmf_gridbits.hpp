@@ -1,7 +1,8 @@
 // dmf_gridbits.hpp — the occupancy bitmask's 8x8x8-tile layout and the step from an int16 log-odds
 // grid to threshold bits, shared by the point-cloud occupancy (occ_bit, dmf_internal.hpp) and the
-// fused grid's consumers (dmf_raycast.hip, dmf_surface.hip, dmf_distance.hip): the tile counts of
-// a grid, cell -> tile and bit index, the 8-cell loader, and the tile mask pass.
+// fused grid's consumers (dmf_raycast.hip, dmf_surface.hip, dmf_distance.hip, dmf_travel.hip): the
+// tile counts of a grid, cell -> tile and bit index, the 8-cell loaders (int16 log-odds, uint32
+// distance field), and the tile mask pass.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,7 +59,29 @@ __device__ inline void for_cells8(const int16_t* __restrict__ p, int nvalid, F&&
   }
 }
 
-// The tile mask pass: NM 1-bit-per-cell masks of an int16 grid in the layout above, one
+// The uint32 counterpart (the distance field's cells): up to 4 consecutive cells at p, of which
+// the first nvalid exist, in one 16-B load when all 4 exist and p is 16-B aligned; and 8 cells as
+// two such groups, so that the tile mask pass reads either grid.
+template <class F>
+__device__ inline void for_cells4(const uint32_t* __restrict__ p, int nvalid, F&& f) {
+  if (nvalid >= 4 && ((uintptr_t)p & 15) == 0) {
+    const uint4 q = *(const uint4*)p;
+    f(0, q.x);
+    f(1, q.y);
+    f(2, q.z);
+    f(3, q.w);
+  } else {
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)  // (the rare path: kept small)
+    for (int k = 0; k < 4 && k < nvalid; ++k) f(k, p[k]);
+  }
+}
+template <class F>
+__device__ inline void for_cells8(const uint32_t* __restrict__ p, int nvalid, F&& f) {
+  for_cells4(p, nvalid, f);
+  if (nvalid > 4) for_cells4(p + 4, nvalid - 4, [&](int k, uint32_t c) { f(k + 4, c); });
+}
+
+// The tile mask pass: NM 1-bit-per-cell masks of an int16 (or uint32) grid in the layout above, one
 // streaming pass.  One workgroup of kMaskThreads per 32 consecutive tiles = 512 words of each mask.
 // Thread (tile j = i & 31, word w = i >> 5) reads the word's 4 y-rows of 8 z-cells (16 B each): a
 // wave's loads are 2 x 4 rows of up to 512 contiguous bytes.  classify(value, k, b) sets bit k of
@@ -66,8 +89,8 @@ __device__ inline void for_cells8(const int16_t* __restrict__ p, int nvalid, F&&
 // words go through LDS so that the workgroup's NM x 2 KiB are stored in order, out[m][word index].
 // word[] returns the thread's own words (tile j, word w); the call holds one workgroup barrier.
 constexpr int kMaskThreads = 512;
-template <int NM, class F>
-__device__ inline void tile_mask_pass(const Geom& g, const GridTiles& tl, const int16_t* __restrict__ L,
+template <int NM, class T, class F>
+__device__ inline void tile_mask_pass(const Geom& g, const GridTiles& tl, const T* __restrict__ L,
                                       uint32_t* const (&out)[NM], uint32_t (&word)[NM], F&& classify) {
   __shared__ uint32_t sw[NM][kMaskThreads];
   const int i = threadIdx.x, j = i & 31, w = i >> 5;
@@ -83,7 +106,7 @@ __device__ inline void tile_mask_pass(const Geom& g, const GridTiles& tl, const 
         if (y < g.n[1]) {
           uint32_t b[NM] = {};
           for_cells8(L + (((int64_t)x * g.n[1] + y) * g.n[2] + z0), g.n[2] - z0,
-                     [&](int k, int c) { classify(c, k, b); });
+                     [&](int k, auto c) { classify(c, k, b); });
           for (int m = 0; m < NM; ++m) word[m] |= b[m] << (8 * dy);
         }
       }

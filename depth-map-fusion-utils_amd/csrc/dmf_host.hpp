@@ -77,6 +77,9 @@ enum ScratchSlot {
   // view gain (dmf_viewgain.hip): the solid and unknown masks, their tile + brick levels, and the
   // masks and gains of the calls that keep them in scratch
   kScVgSolid, kScVgUnknown, kScVgCoarse, kScVgSeen, kScVgGain,
+  // the travel field (dmf_travel.hip): the traversable mask and its tile level, the two active-tile
+  // lists with their "queued" bits, the counters and list lengths, and the host forms' field
+  kScTrFine, kScTrCoarse, kScTrQueue, kScTrCtl, kScTrHops,
   // brick-owned fusion (dmf_fuse.hip): one block, buffer b of staging slot s at bk_key(b, s)
   kScBkFirst, kScBkEnd = kScBkFirst + 2 * kBkBufCount
 };

@@ -278,6 +278,8 @@ struct dmf_volume {
   int fuse_variant = 0;
   const char* last_kernel = nullptr;  // the fusion kernel of the latest call
   int64_t knob[DMF_KNOB_COUNT] = {};
+  // the latest travel-field call (dmf_grid_travel_stats): rounds, launches, tile activations, cell updates
+  uint64_t travel_stats[4] = {0, 0, 0, 0};
   // scratch arena
   std::vector<std::pair<void*, size_t>> scratch;
 

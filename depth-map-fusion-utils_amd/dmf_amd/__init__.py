@@ -34,6 +34,9 @@ NO_CELL = np.uint64(0xFFFFFFFFFFFFFFFF)
 # VoxelVolume.distance_field / segment_clearance: no solid cell in the grid / no cell on the segment
 # (DMF_NO_DIST, include/dmf.h; no squared distance in a grid of at most 2048 cells per axis is all ones)
 NO_DIST = np.uint32(0xFFFFFFFF)
+# VoxelVolume.travel_field: a cell that is not traversable or not reachable (DMF_NO_PATH, include/dmf.h;
+# a grid of at most 2^31 cells has no hop count of all ones)
+NO_PATH = np.uint32(0xFFFFFFFF)
 
 
 def degree(radian):
@@ -320,6 +323,102 @@ class VoxelVolume:
         pa, pb = pa.reshape(-1, 3), pb.reshape(-1, 3)
         out = np.empty(pa.shape[0], np.uint32)
         check(self._L.dmf_grid_clearance(self._h, ptr(d2), ptr(pa), ptr(pb), pa.shape[0], ptr(out)))
+        return out
+
+    # -- travel field over a distance field, the path back and the travel cost map, on the GPU
+    def _field(self, a, name):
+        n = int(np.prod(self.dims))
+        f = np.asarray(a)
+        if f.dtype != np.uint32 or f.size != n:
+            raise ValueError(f"{name} must be uint32 with {n} cells (x-major over dims {tuple(self.dims)}), "
+                             f"got {f.dtype} with {f.size}")
+        return np.ascontiguousarray(f).reshape(-1)
+
+    @staticmethod
+    def _cells(a, name):
+        c = np.asarray(a)
+        if c.dtype.kind not in "iu" or c.ndim != 2 or c.shape[1] != 3:
+            raise ValueError(f"{name} must be integer cell indices of shape (n, 3), got {c.dtype} {c.shape}")
+        return np.ascontiguousarray(c, np.int32)
+
+    def travel_field(self, dist2, radius2, seeds, info=False):
+        """The travel field of the seed cells `seeds` (integers, (n, 3)) over the field `dist2` of
+        distance_field -> uint32 (xdim, ydim, zdim): per cell the least number of face-to-face steps
+        from any valid seed through cells with dist2 >= radius2 (both ends included), 0 on a valid
+        seed, NO_PATH where a cell is not traversable or not reachable.  Seeds outside the grid or
+        on blocked cells are ignored.  Steps cross faces only: a hop count over-estimates the
+        Euclidean length, in cells, by up to sqrt(3).  info=True also returns (traversable cells,
+        reached cells, largest finite hop count)."""
+        d2 = self._field(dist2, "dist2")
+        s = self._cells(seeds, "seeds")
+        if not 0 <= int(radius2) <= 0xFFFFFFFF:
+            raise ValueError(f"radius2 must fit uint32, got {radius2}")
+        out = np.empty(tuple(self.dims), np.uint32)
+        cnt = np.zeros(3, np.uint64)
+        check(self._L.dmf_grid_travel(self._h, ptr(d2), int(radius2), ptr(s) if s.shape[0] else None, s.shape[0],
+                                      ptr(out), ptr(cnt)))
+        return (out, tuple(int(c) for c in cnt)) if info else out
+
+    def path_to(self, hops, target):
+        """The path from the cell `target` back to a seed in the field `hops` of travel_field ->
+        int32 (n, 3), target first: n = hops[target] + 1 cells, each step to the first face
+        neighbour in the order -x +x -y +y -z +z that holds one hop less; (0, 3) for a target
+        outside the grid or with NO_PATH."""
+        h = self._field(hops, "hops")
+        t = np.asarray(target)
+        if t.dtype.kind not in "iu" or t.shape != (3,):
+            raise ValueError(f"target must be one integer cell index (3,), got {t.dtype} {t.shape}")
+        t = np.ascontiguousarray(t, np.int32)
+        nx, ny, nz = self.dims
+        if not (0 <= t[0] < nx and 0 <= t[1] < ny and 0 <= t[2] < nz):
+            return np.zeros((0, 3), np.int32)
+        k = int(h[(int(t[0]) * ny + int(t[1])) * nz + int(t[2])])
+        if k == int(NO_PATH):
+            return np.zeros((0, 3), np.int32)
+        out = np.zeros((min(k + 1, h.size), 3), np.int32)
+        n = C.c_int64(0)
+        check(self._L.dmf_grid_path(self._h, ptr(h), ptr(t), ptr(out), out.shape[0], C.addressof(n)))
+        return out[:n.value]
+
+    def travel_cost_map(self, dist2, radius2, cells):
+        """The V x V travel cost map of the cells `cells` (integers, (V, 3)) -> int32 (V, V):
+        entry [i][j] = the hop count from cells[i] to cells[j] through cells with dist2 >= radius2,
+        INT_MAX where there is no path -- the fused grid's counterpart of collisionCostMap, with
+        detours.  One travel field per row, made on the device into one reused buffer; only the
+        row's V entries come back."""
+        d2 = self._field(dist2, "dist2")
+        c = self._cells(cells, "cells")
+        if not 0 <= int(radius2) <= 0xFFFFFFFF:
+            raise ValueError(f"radius2 must fit uint32, got {radius2}")
+        V = c.shape[0]
+        nx, ny, nz = self.dims
+        out = np.full((V, V), 2147483647, np.int32)
+        if V == 0:
+            return out
+        inside = ((c >= 0) & (c < np.array([nx, ny, nz]))).all(axis=1)
+        flat = (c[:, 0].astype(np.int64) * ny + c[:, 1]) * nz + c[:, 2]
+        bufs = []
+
+        def alloc(nbytes):
+            p = C.c_void_p()
+            check(self._L.dmf_device_malloc(self._h, C.addressof(p), max(int(nbytes), 8)))
+            bufs.append(p.value)
+            return p.value
+
+        try:
+            d_d2, d_hops, d_seeds = alloc(d2.nbytes), alloc(d2.nbytes), alloc(c.nbytes)
+            check(self._L.dmf_memcpy_h2d(self._h, d_d2, ptr(d2), d2.nbytes))
+            check(self._L.dmf_memcpy_h2d(self._h, d_seeds, ptr(c), c.nbytes))
+            one = np.zeros(1, np.uint32)
+            for i in range(V):
+                check(self._L.dmf_grid_travel_device(self._h, d_d2, int(radius2), d_seeds + 12 * i, 1, d_hops, None))
+                for j in np.flatnonzero(inside):
+                    check(self._L.dmf_memcpy_d2h(self._h, ptr(one), d_hops + 4 * int(flat[j]), 4))
+                    if one[0] != NO_PATH:
+                        out[i, j] = int(one[0])
+        finally:
+            for p in bufs:
+                self._L.dmf_device_free(self._h, p)
         return out
 
     @property

@@ -144,6 +144,11 @@ SIGNATURES = {
     "dmf_grid_distance_device": (C.c_int, [_vp, _p, _i32, _p, _p]),
     "dmf_grid_clearance": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
     "dmf_grid_clearance_device": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
+    "dmf_grid_travel": (C.c_int, [_vp, _p, C.c_uint32, _p, _i64, _p, _p]),
+    "dmf_grid_travel_device": (C.c_int, [_vp, _p, C.c_uint32, _p, _i64, _p, _p]),
+    "dmf_grid_path": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
+    "dmf_grid_path_device": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
+    "dmf_grid_travel_stats": (C.c_int, [_vp, _p]),
     "dmf_fuse_counter_cells": (C.c_int, [_vp, _p]),
     "dmf_fuse_counters_to_linear_device": (C.c_int, [_vp, _p, _p]),
     "dmf_fuse_reserve": (C.c_int, [_vp, _p, _i32, C.c_uint64]),

@@ -501,6 +501,51 @@ int dmf_grid_clearance(dmf_volume* v, const uint32_t* dist2, const float* a, con
 int dmf_grid_clearance_device(dmf_volume* v, const uint32_t* d_dist2, const float* d_a, const float* d_b,
                               int64_t n, uint32_t* d_clear2);
 
+/* Travel field over a distance field of this volume: can a body of radius r reach
+ * a cell from the seeds at all, and in how many steps?  dist2 is a field of dmf_grid_distance*
+ * (DMF_NO_DIST allowed); a cell is traversable iff dist2 >= radius2 (radius2 = 1: every non-solid
+ * cell; 0: every cell); seeds are n_seeds x 3 int32 cell indices.
+ *   hops[x][y][z] (uint32, x-major like the grid) = the least number of steps of a path from any
+ *   valid seed to the cell, a step going to one of the six face neighbours inside the grid and
+ *   every cell of the path, both ends included, being traversable; 0 on a valid seed; DMF_NO_PATH
+ *   on every cell that is not traversable or not reachable.
+ * A seed outside the grid or on a cell that is not traversable is ignored, duplicates are allowed,
+ * and no valid seed (n_seeds = 0 too) gives a field of DMF_NO_PATH and DMF_OK.  Steps cross faces
+ * only, so hops over-estimates the Euclidean length of the best path, in cells, by up to sqrt(3).
+ * info3 (may be NULL) receives 3 counters, written, not accumulated: {traversable cells, reached
+ * cells, the largest finite hop count (0 when nothing is reached)}.  Only the volume's dims are
+ * used; its point-cloud occupancy is neither read nor changed.
+ * Host form: host pointers, synchronises.  Device form: device pointers on the volume's stream;
+ * d_hops is also the rounds' work buffer.  The relaxation runs in rounds, one launch each, and the
+ * host has to learn when a round changed nothing, so the device form WAITS FOR ITS OWN WORK like
+ * dmf_next_best_views_device; d_info3 is complete when it returns.  Scratch (1 bit per cell and 8
+ * B per 8x8x8 tile) is allocated when it must grow and reused.  Rounds are bounded by the
+ * traversable count; past the bound the call returns DMF_ERR_DEVICE_CHECK.
+ * Null v / dist2 / hops, null seeds with n_seeds > 0 and n_seeds < 0 are DMF_ERR_INVALID (checked
+ * before the volume is touched); an unconstructed volume is DMF_ERR_STATE; more than 2048 cells
+ * on an axis, or more than 2^31 cells in all, is DMF_ERR_RANGE.
+ *
+ * Path back from a cell: target3 is one int32 cell index, hops a field of the call above.  The
+ * path is the cell sequence target, ..., seed of hops[target] + 1 cells: from a cell with value
+ * k > 0 the next cell is the first face neighbour, in the order -x +x -y +y -z +z and skipping
+ * those outside the grid, that holds k - 1.  A target outside the grid or with DMF_NO_PATH gives 0
+ * cells and DMF_OK.  The walk ends on any field: where no neighbour holds k - 1 it stops and
+ * returns what it has.  cells is cap x 3 int32.  Capacity as in dmf_grid_surface: the device form
+ * writes the first min(length, cap) cells, nothing at or past cap, and always *d_n (compare it
+ * with cap), and only enqueues; the host form returns DMF_ERR_CAPACITY with *n = the need and
+ * cells untouched when cap < length, except that cap = 0 with NULL cells is the size query
+ * (DMF_OK).  Null v / hops / target3 / n, cap < 0 and NULL cells with cap > 0 are DMF_ERR_INVALID;
+ * the volume is checked as above. */
+#define DMF_NO_PATH UINT32_MAX
+int dmf_grid_travel(dmf_volume* v, const uint32_t* dist2, uint32_t radius2, const int32_t* seeds, int64_t n_seeds,
+                    uint32_t* hops, uint64_t* info3);
+int dmf_grid_travel_device(dmf_volume* v, const uint32_t* d_dist2, uint32_t radius2, const int32_t* d_seeds,
+                           int64_t n_seeds, uint32_t* d_hops, uint64_t* d_info3);
+int dmf_grid_path(dmf_volume* v, const uint32_t* hops, const int32_t* target3, int32_t* cells, int64_t cap,
+                  int64_t* n);
+int dmf_grid_path_device(dmf_volume* v, const uint32_t* d_hops, const int32_t* d_target3, int32_t* d_cells,
+                         int64_t cap, uint64_t* d_n);
+
 /* ---- multi-GPU merge over RCCL ------------------------
  * Poses shard across ranks, each rank fuses into its own replica of the counters, and
  * the replicas merge with integer collectives (bit-identical to one rank fusing all

@@ -72,6 +72,12 @@ enum dmf_knob {
 int dmf_volume_set_knob(dmf_volume* v, int32_t knob, int64_t value);
 int dmf_volume_get_knob(const dmf_volume* v, int32_t knob, int64_t* value);
 
+/* The volume's latest dmf_grid_travel* call: stats4 = {rounds that had work, kernel launches
+ * (rounds are launched in batches, so the last ones find an empty list), tile activations, cell
+ * updates}; the last two are counted only by a library built with -DDMF_EXP_STATS and are 0
+ * otherwise. */
+int dmf_grid_travel_stats(const dmf_volume* v, uint64_t* stats4);
+
 /* OccupancyGrid: downloadReorganizedCloud (modes 2 / 3 of dmf_ogrid_download) iterates fixed-point
  * rounds and, when they do not settle within the cap, runs the sequential loop on one lane; both
  * give the same cloud.  rounds: the rounds the grid's latest mode-2/3 download ran until its fixed
