@@ -64,22 +64,48 @@ __host__ __device__ inline void pack_ray(const int64_t qs[3], const int64_t qe[3
   B = (uint64_t)qe[0] | ((uint64_t)qe[1] << 19) | ((uint64_t)qe[2] << 38) | ((uint64_t)1 << 63);
 }
 
-// The QRay of quantised endpoints qs, qe (what decode_ray gives for their record).
+// The same record as four dwords (A = a[0] | a[1] << 32, B = b[0] | b[1] << 32) from 32-bit
+// coordinates: pass A's form, no 64-bit shifts.
+__host__ __device__ inline void pack_ray32(const int32_t qs[3], const int32_t qe[3], bool end_inside, uint32_t a[2],
+                                           uint32_t b[2]) {
+  const uint32_t s0 = (uint32_t)qs[0], s1 = (uint32_t)qs[1], s2 = (uint32_t)qs[2];
+  const uint32_t e0 = (uint32_t)qe[0], e1 = (uint32_t)qe[1], e2 = (uint32_t)qe[2];
+  a[0] = s0 | s1 << 19;
+  a[1] = s1 >> 13 | s2 << 6 | (end_inside ? 1u << 31 : 0u);
+  b[0] = e0 | e1 << 19;
+  b[1] = e1 >> 13 | e2 << 6 | 1u << 31;
+}
+
+// |x - y| for x, y >= 0: one v_sad_u32 on the device (the compiler's own form is two subtractions
+// and a maximum).
+__host__ __device__ inline int32_t absdiff(int32_t x, int32_t y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int32_t r;
+  asm("v_sad_u32 %0, %1, %2, 0" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+#else
+  return x > y ? x - y : y - x;
+#endif
+}
+
+// The QRay of quantised endpoints qs, qe >= 0 (what decode_ray gives for their record).  The
+// direction of an axis is the sign of ce - cs, taken once: st is that difference clamped to
+// [-1, 1], and the first-crossing numerator of oracle.cpp dda_ray, 2((cs + 1)Q - qs) moving up and
+// 2(qs - cs Q) + 1 otherwise, is 2Q - 2f and 2f + 1 of the sub-cell fraction f = qs mod Q.
 __host__ __device__ inline void qray_from(const int32_t qs[3], const int32_t qe[3], bool end_inside, QRay& r) {
   r.end_inside = end_inside;
-  r.nsteps = 0;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     r.cs[a] = qs[a] >> 8;
     r.ce[a] = qe[a] >> 8;
-    const int32_t dq = qe[a] - qs[a];
-    r.adq[a] = dq < 0 ? -dq : dq;
-    r.st[a] = r.ce[a] > r.cs[a] ? 1 : (r.ce[a] < r.cs[a] ? -1 : 0);
-    r.n[a] = r.ce[a] > r.cs[a] ? r.ce[a] - r.cs[a] : r.cs[a] - r.ce[a];
-    // oracle.cpp dda_ray: moving up 2((cs+1)Q - qs), moving down 2(qs - cs Q) + 1
-    r.h0[a] = r.st[a] > 0 ? 2 * ((r.cs[a] + 1) * (int32_t)kQ - qs[a]) : 2 * (qs[a] - r.cs[a] * (int32_t)kQ) + 1;
-    r.nsteps += r.n[a];
+    r.adq[a] = absdiff(qe[a], qs[a]);
+    const int32_t d = r.ce[a] - r.cs[a];
+    r.st[a] = d < -1 ? -1 : (d > 1 ? 1 : d);
+    r.n[a] = absdiff(r.ce[a], r.cs[a]);
+    const int32_t f2 = 2 * (qs[a] & ((int32_t)kQ - 1));
+    r.h0[a] = d > 0 ? 2 * (int32_t)kQ - f2 : f2 + 1;
   }
+  r.nsteps = r.n[0] + r.n[1] + r.n[2];
 }
 
 __host__ __device__ inline void decode_ray(uint64_t A, uint64_t B, QRay& r) {
@@ -307,15 +333,24 @@ struct Coarse {
   int32_t total;                      // boundary crossings of the whole ray
 };
 
+// The fine crossing of axis a that is its first brick-boundary crossing: kB - 1 - off moving up,
+// off otherwise (off = the start cell's offset in its brick).  The direction is qray_from's own
+// test of ce - cs.
+__host__ __device__ inline int32_t first_boundary(const QRay& r, int a) {
+  const int32_t off = r.cs[a] & (kB - 1);
+  return r.ce[a] - r.cs[a] > 0 ? kB - 1 - off : off;
+}
+
+// Brick boundaries the ray crosses along an axis whose first one is crossing k0: none when
+// n <= k0 (a non-moving axis has n = 0), else (n - 1 - k0) / kB + 1 -- which is
+// (n + kB - 1 - k0) >> kLog in both cases, as 0 <= k0 <= kB - 1.
+__host__ __device__ inline int32_t boundaries_from(int32_t n, int32_t k0) { return (n + (kB - 1 - k0)) >> kLog; }
+
 // Brick boundaries the ray crosses (the coarse walk's step count).
 __host__ __device__ inline int32_t coarse_total(const QRay& r) {
   int32_t total = 0;
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int32_t off = r.cs[a] & (kB - 1);
-    const int32_t k0 = r.st[a] > 0 ? kB - 1 - off : off;  // first boundary crossing
-    if (r.st[a] != 0 && r.n[a] > k0) total += (r.n[a] - 1 - k0) / kB + 1;
-  }
+  for (int a = 0; a < 3; ++a) total += boundaries_from(r.n[a], first_boundary(r, a));
   return total;
 }
 
@@ -382,11 +417,11 @@ struct Coarse32 {
 
 __host__ __device__ inline void coarse_init32(const QRay& r, Coarse32& w) {
   int32_t H[3];  // <= 2Q kB = 2^14: 32x32-bit products below
-  w.total = coarse_total(r);
+  w.total = 0;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const int32_t off = r.cs[a] & (kB - 1);
-    const int32_t k0 = r.st[a] > 0 ? kB - 1 - off : off;  // first boundary crossing
+    const int32_t k0 = first_boundary(r, a);  // (once for the count and for H)
+    w.total += boundaries_from(r.n[a], k0);
     H[a] = r.h0[a] + (int32_t)(2 * kQ) * k0;
   }
   auto pr = [&](int a, int b) -> int32_t {

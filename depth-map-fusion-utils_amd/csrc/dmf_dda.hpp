@@ -1,26 +1,17 @@
 // dmf_dda.hpp — the exact integer 3D-DDA of a probe ray and the tiled counter
 // layout, shared by the fusion kernels (dmf_fuse.hip), the log-odds ray-cast (dmf_raycast.hip)
-// and the segment clearance (dmf_distance.hip): clip and quantise origin -> endpoint, the int32
-// walk state, one selection step, the walk in scalars, the per-pixel ray of a depth frame, and the
-// exact jump out of an aligned cube of cells (rc_jump: the ray-cast's and the view gain's).
+// and the segment clearance (dmf_distance.hip): clip and quantise origin -> endpoint (dmf_quant.hpp,
+// host-compilable), the int32 walk state, one selection step, the walk in scalars, the per-pixel
+// ray of a depth frame, and the exact jump out of an aligned cube of cells (rc_jump: the
+// ray-cast's and the view gain's).
 #pragma once
 #include "dmf_internal.hpp"
+#include "dmf_quant.hpp"
 
 namespace dmf {
 
-constexpr int64_t kQ = 256;  // fixed-point sub-cell resolution (1/256 cell)
-
-__device__ inline int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ inline int32_t clamp32(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// (int64_t) floor(x) as the oracle's x86 conversion gives it (cvttsd2si: NaN and |x| >= 2^63
-// -> INT64_MIN), saturated to +-2^30: a v_cvt_i32_f64 and a select instead of the int64
-// conversion sequence.  Every use clamps the result into [0, n * kQ) with n * kQ <= 2^19
-// (fusion grids <= 2048 cells per axis, check_fuse), so the clamped values are identical.
-__device__ inline int32_t floor_sat32(double x) {
-  const double f = floor(x);
-  return fabs(f) < 9223372036854775808.0 ? (int32_t)fmin(fmax(f, -1073741824.0), 1073741824.0) : -(1 << 30);
-}
+// (kQ, grid_coord, the endpoint acceptance and the clip / quantisation:
+// dmf_quant.hpp, which the CPU self-test compiles too)
 
 __device__ inline void atomic_add_dev(int32_t* p, int32_t v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -95,80 +86,15 @@ struct Walk {
   }
 };
 
-// (x - min) / delta in double (oracle.cpp dda_ray); a power-of-two delta divides exactly
-// as a multiplication by its (exact) reciprocal, as in bin_axis
-__device__ inline double grid_coord(const Geom& g, int a, float x) {
-  const double t = (double)x - g.mn[a];
-  return g.pow2 ? t * g.inv[a] : t / g.dl[a];
-}
-
-// Grid coordinates of the ray origin.
-__device__ inline void grid_origin(const Geom& g, const float O[3], double go[3]) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) go[a] = grid_coord(g, a, O[a]);
-}
-
-// Clip O->E to the grid and quantise the clipped endpoints to 1/256 cell (clamped
-// into their cells).  Mirrors oracle.cpp dda_ray() lines 752-780 operation for
-// operation; go = grid_origin(O) (one per pose: callers hoist it).  Returns false when
-// the ray misses the grid.
-// A ray that ends inside the grid has t1 overwritten by 1, so of each axis' two slab
-// quotients only the entry one, min(ta, tb), matters, and only when it can exceed t0 >= 0:
-// (0 - go) / D for D > 0, which is <= 0 unless go < 0, and (n - go) / D for D < 0, which is
-// <= 0 unless go > n (division is monotone and keeps the sign) -- so the other divisions
-// are skipped with identical t0 and t1.
-__device__ inline bool dda_quantize_go(const Geom& g, const double go[3], const float E[3], bool end_inside,
-                                       int64_t qs[3], int64_t qe[3]) {
-  double ge[3], D[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    ge[a] = grid_coord(g, a, E[a]);
-    D[a] = ge[a] - go[a];
-  }
-  double t0 = 0.0, t1 = 1.0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (D[a] == 0.0) {
-      if (go[a] < 0.0 || go[a] >= (double)g.n[a]) return false;
-    } else if (end_inside) {
-      if (D[a] > 0.0 ? go[a] < 0.0 : go[a] > (double)g.n[a]) {
-        const double lo = (D[a] > 0.0 ? 0.0 - go[a] : (double)g.n[a] - go[a]) / D[a];
-        if (lo > t0) t0 = lo;
-      }
-    } else {
-      double ta = (0.0 - go[a]) / D[a];
-      double tb = ((double)g.n[a] - go[a]) / D[a];
-      if (ta > tb) { const double tt = ta; ta = tb; tb = tt; }
-      if (ta > t0) t0 = ta;
-      if (tb < t1) t1 = tb;
-    }
-  }
-  if (end_inside) { t1 = 1.0; if (t0 > 1.0) t0 = 1.0; }
-  if (t0 > t1) return false;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double gs = go[a] + t0 * D[a];
-    const double gx = end_inside ? ge[a] : go[a] + t1 * D[a];
-    const int32_t n = (int32_t)g.n[a], Q = (int32_t)kQ;
-    const int32_t cs = clamp32(floor_sat32(gs), 0, n - 1);
-    const int32_t ce = end_inside ? floor_sat32(ge[a]) : clamp32(floor_sat32(gx), 0, n - 1);
-    qs[a] = clamp32(floor_sat32(gs * (double)kQ), cs * Q, cs * Q + Q - 1);
-    qe[a] = clamp32(floor_sat32(gx * (double)kQ), ce * Q, ce * Q + Q - 1);
-  }
-  return true;
-}
-
-__device__ inline bool dda_quantize(const Geom& g, const float O[3], const float E[3], bool end_inside, int64_t qs[3],
-                                    int64_t qe[3]) {
-  double go[3];
-  grid_origin(g, O, go);
-  return dda_quantize_go(g, go, E, end_inside, qs, qe);
-}
-
-// Clip/quantise, then set up the walk state (oracle.cpp dda_ray lines 781-806).
+// Clip/quantise (dmf_quant.hpp), then set up the walk state (oracle.cpp dda_ray lines 781-806).
+// end_inside = endpoint_inside(g, E).
 __device__ inline bool dda_setup(const Geom& g, const float O[3], const float E[3], bool end_inside, Ray& R) {
-  int64_t qs[3], qe[3];
-  if (!dda_quantize(g, O, E, end_inside, qs, qe)) return false;
+  double go[3], ge[3];
+  grid_origin(g, O, go);
+  grid_origin(g, E, ge);
+  int32_t qs32[3], qe32[3];
+  if (!dda_quantize_ge(g, go, ge, end_inside, qs32, qe32)) return false;
+  const int64_t qs[3] = {qs32[0], qs32[1], qs32[2]}, qe[3] = {qe32[0], qe32[1], qe32[2]};
   int64_t cs[3], ce[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -202,17 +128,6 @@ __device__ inline bool dda_setup(const Geom& g, const float O[3], const float E[
   return true;
 }
 
-// The acceptance of integratePointCloud(cloud, normals) (Volume.hpp:199-228):
-// validPoints(E) && validCoords(getVoxel(E)).  validPoints as float compares (vlo / vhi,
-// dmf_geom.hpp; a NaN endpoint, from a non-finite pose, is outside: the reference's getVoxel
-// gives INT_MIN for it, which validCoords rejects), then getVoxel in double.
-__device__ inline bool endpoint_inside(const Geom& g, const float E[3]) {
-  const bool in = (E[0] >= g.vlo[0]) & (E[0] <= g.vhi[0]) & (E[1] >= g.vlo[1]) & (E[1] <= g.vhi[1]) &
-                  (E[2] >= g.vlo[2]) & (E[2] <= g.vhi[2]);
-  if (!in) return false;
-  return valid_coords(g, bin_axis(g, 0, E[0]), bin_axis(g, 1, E[1]), bin_axis(g, 2, E[2]));
-}
-
 // Per-pixel ray: back-projection (Camera.hpp:24-45) + binning of the endpoint
 // (Volume.hpp:150-156, 199-228) + DDA setup.  Returns the update count (0 = no ray).
 __device__ inline int pixel_ray(const Geom& g, const CamP& cam, const uint16_t* __restrict__ depth,
@@ -237,7 +152,7 @@ __device__ inline int pixel_ray(const Geom& g, const CamP& cam, const uint16_t* 
 // The brick path's ray record: pixel_ray up to the quantised endpoints, with the pose's grid
 // origin already computed (go = grid_origin of poses[p]'s translation; d < 0: outside the frame).
 __device__ inline bool pixel_quant_go(const Geom& g, const CamP& cam, int d, const float Tf[12], const double go[3],
-                                      int r, int c, int dmin, int dmax, int64_t qs[3], int64_t qe[3], bool& inside,
+                                      int r, int c, int dmin, int dmax, int32_t qs[3], int32_t qe[3], bool& inside,
                                       bool& valid) {
   valid = false;
   inside = false;
@@ -246,8 +161,7 @@ __device__ inline bool pixel_quant_go(const Geom& g, const CamP& cam, int d, con
   float pc[3], E[3];
   project(cam, r, c, d, pc);
   xform(Tf, pc[0], pc[1], pc[2], E);
-  inside = endpoint_inside(g, E);
-  return dda_quantize_go(g, go, E, inside, qs, qe);
+  return dda_quantize_go(g, go, E, &inside, qs, qe);
 }
 
 __device__ inline int pixel_depth(const CamP& cam, const uint16_t* __restrict__ depth, int p, int r, int c) {

@@ -51,15 +51,21 @@ struct DepthSrc {
     const float O[3] = {f.Tf[3], f.Tf[7], f.Tf[11]};
     grid_origin(g, O, go);
   }
+  // (p and q are the same in every lane of the wave -- pass A's caller makes them scalars -- so
+  // the packet's row and column, two integer divisions, and the 64-bit base of its depth rows are
+  // scalar work; a lane adds its own offset in the 8x8 block, 32 bits beside the scalar base)
   __device__ Sample load(int p, int q, int l) const {
     Sample s;
-    s.r = (q / packets_x) * 8 + (l >> 3);
-    s.c = (q % packets_x) * 8 + (l & 7);
-    s.d = pixel_depth(cam, depth, p, s.r, s.c);
+    const int qy = q / packets_x, r0 = qy * 8, c0 = (q - qy * packets_x) * 8;
+    s.r = r0 + (l >> 3);
+    s.c = c0 + (l & 7);
+    const uint16_t* const block = depth + (((int64_t)p * cam.H + r0) * cam.W + c0);
+    const uint32_t off = (uint32_t)(l >> 3) * (uint32_t)cam.W + (uint32_t)(l & 7);
+    s.d = (s.r >= cam.H || s.c >= cam.W) ? -1 : (int)block[off];
     return s;
   }
-  __device__ bool quant(const Geom& g, const Frame& f, const double go[3], const Sample& s, int64_t qs[3],
-                        int64_t qe[3], bool& inside, bool& valid) const {
+  __device__ bool quant(const Geom& g, const Frame& f, const double go[3], const Sample& s, int32_t qs[3],
+                        int32_t qe[3], bool& inside, bool& valid) const {
     return pixel_quant_go(g, cam, s.d, f.Tf, go, s.r, s.c, dmin, dmax, qs, qe, inside, valid);
   }
   __device__ int ray(const Geom& g, int p, int q, int l, Ray& R, bool& valid) const {
@@ -104,13 +110,12 @@ struct PointSrc {
     s.E[2] = e[2];
     return s;
   }
-  __device__ bool quant(const Geom& g, const Frame& f, const double go[3], const Sample& s, int64_t qs[3],
-                        int64_t qe[3], bool& inside, bool& valid) const {
+  __device__ bool quant(const Geom& g, const Frame& f, const double go[3], const Sample& s, int32_t qs[3],
+                        int32_t qe[3], bool& inside, bool& valid) const {
     inside = false;
     valid = f.live & s.ok & finite3(s.E);
     if (!valid) return false;
-    inside = endpoint_inside(g, s.E);
-    return dda_quantize_go(g, go, s.E, inside, qs, qe);
+    return dda_quantize_go(g, go, s.E, &inside, qs, qe);
   }
   __device__ int ray(const Geom& g, int p, int q, int l, Ray& R, bool& valid) const {
     float O[3];
@@ -509,12 +514,17 @@ __device__ inline void bk_rays_wg(const BkRaysArgs<Src>& A_, unsigned wg, uint32
   const int nwords = HASH ? (int)hmask + 1 : (H16 ? (bg.nbricks + 1) >> 1 : bg.nbricks);
   for (int i = threadIdx.x; i < nwords; i += blockDim.x) hist[i] = HASH ? kHashEmpty : 0u;
   __syncthreads();
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = blockDim.x >> 6;
+  // the wave's index as a scalar: the packet number, the packet's place in its frame and the
+  // bases of its loads and stores are then scalar work, and the packet loop a scalar loop (taken
+  // from threadIdx.x they were vector arithmetic, two integer divisions per packet among it)
+  const int w = bk::wave_uniform((int)(threadIdx.x >> 6)), l = threadIdx.x & 63, nw = blockDim.x >> 6;
   const int pw = (int)(wg / (unsigned)A_.wg_pose);
   const int q0 = (int)(wg - (unsigned)pw * (unsigned)A_.wg_pose) * A_.span;
   const int64_t pk0 = (int64_t)pw * A_.packets_pose + q0,
                 pk1 = (int64_t)pw * A_.packets_pose + min(A_.packets_pose, q0 + A_.span);
-  unsigned long long upd = 0, nvalid = 0, nhit = 0;
+  // per lane in 32 bits: a wave takes at most span <= 1023 packets (span * 64 <= 65535, bk_plan)
+  // of at most 3 * 2048 + 1 updates a ray
+  uint32_t upd = 0, nvalid = 0, nhit = 0;
   // (loading the next packet's depth one packet ahead measured slower: 0.79 -> 0.84 ms)
   double go[3];
   typename Src::Frame fr;  // the workgroup's frame (DepthSrc: its pose, held in registers)
@@ -523,22 +533,17 @@ __device__ inline void bk_rays_wg(const BkRaysArgs<Src>& A_, unsigned wg, uint32
     const int p = pw;
     const int q = (int)(pk - (int64_t)p * A_.packets_pose);
     const typename Src::Sample sm = A_.src.load(p, q, l);
-    int64_t qs[3], qe[3];
+    int32_t qs[3], qe[3];
     bool inside, valid;
-    ulonglong2 rec;
-    rec.x = 0;
-    rec.y = 0;
+    uint4 rec = make_uint4(0u, 0u, 0u, 0u);  // the ray record (A.lo, A.hi, B.lo, B.hi of pack_ray)
     uint64_t path = 0;  // the crossing axes of the coarse walk (pass B replays them)
     if (A_.src.quant(g, fr, go, sm, qs, qe, inside, valid)) {
-      uint64_t A, B;
-      bk::pack_ray(qs, qe, inside, A, B);
-      rec.x = A;
-      rec.y = B;
+      uint32_t ra[2], rb[2];
+      bk::pack_ray32(qs, qe, inside, ra, rb);
+      rec = make_uint4(ra[0], ra[1], rb[0], rb[1]);
       bk::QRay R;
-      const int32_t qs32[3] = {(int32_t)qs[0], (int32_t)qs[1], (int32_t)qs[2]},
-                    qe32[3] = {(int32_t)qe[0], (int32_t)qe[1], (int32_t)qe[2]};
-      bk::qray_from(qs32, qe32, inside, R);  // = decode_ray(A, B), without the round trip
-      upd += (unsigned long long)(R.nsteps + 1);
+      bk::qray_from(qs, qe, inside, R);  // = decode_ray(A, B), without the round trip
+      upd += (uint32_t)(R.nsteps + 1);
       nhit += inside ? 1 : 0;
       path = bk_coarse(bg, R, [&](int b) {
         // (pass A 0.72 -> 0.67 ms at 512^3: one aggregation step instead of a loop over every
@@ -548,8 +553,9 @@ __device__ inline void bk_rays_wg(const BkRaysArgs<Src>& A_, unsigned wg, uint32
       });
     }
     nvalid += valid ? 1 : 0;
-    A_.rays[pk * 64 + l] = rec;
-    A_.paths[pk * 64 + l] = path;
+    // (the packet's scalar base, the lane's slot beside it)
+    reinterpret_cast<uint4*>(A_.rays + pk * 64)[l] = rec;
+    (A_.paths + pk * 64)[l] = path;
   }
   __syncthreads();
   if (HASH && sh[1]) {  // table full: k_bk_rays_recover redoes this workgroup
@@ -594,7 +600,7 @@ __device__ inline void bk_rays_wg(const BkRaysArgs<Src>& A_, unsigned wg, uint32
   if (threadIdx.x == 0) row[0] = sh[0];
   for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
   if (l == 0 && mine) atomicAdd(&A_.pose_pairs[pw], mine);
-  if (stats) wave_stats(stats, upd, nvalid, nhit);
+  if (stats) wave_stats(stats, upd, nvalid, nhit);  // (widened to 64 bits here, once)
 }
 
 template <bool H16, class Src>
