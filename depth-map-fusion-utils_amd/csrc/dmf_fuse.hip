@@ -2426,6 +2426,10 @@ int dmf_fuse_get_variant(const dmf_volume* v, int32_t* variant) {
 int dmf_volume_set_knob(dmf_volume* v, int32_t knob, int64_t value) {
   if (!v) return fail(DMF_ERR_INVALID, "null volume");
   if (knob < 1 || knob >= DMF_KNOB_COUNT) return fail(DMF_ERR_INVALID, "unknown knob %d", knob);
+  // a kernel choice names a kernel (an unknown value used to run the default silently)
+  if ((knob == DMF_KNOB_REVERSE_KERNEL && (value < 0 || value > 5)) ||
+      (knob == DMF_KNOB_FWD_KERNEL && (value < 0 || value > 2)))
+    return fail(DMF_ERR_INVALID, "knob %d: no kernel %lld", knob, (long long)value);
   if (knob == DMF_KNOB_BDIST_CAP) {
     if (value < 0 || value > 255) return fail(DMF_ERR_INVALID, "brick distance cap %lld not in 0..255 (0 = default)", (long long)value);
     const int cap = value ? (int)value : kBrickDistCapDefault;

@@ -77,6 +77,16 @@ __host__ __device__ inline int bin_axis(const Geom& g, int a, float x) {
   return (int)floor(q);
 }
 
+// getVoxel of a point inside the volume in the reference's double arithmetic (bin_axis).
+// (The certified float bins bin_axis_f below, exact by tools/binning_selftest.cpp,
+// measured SLOWER in the reverse march: 8.35 vs 7.57 ms per 128-pose batch -- gfx950 runs
+// the fp64 add / mul / floor / converts at the non-packed fp32 rate)
+__host__ __device__ inline void bin_point(const Geom& g, const float p[3], int& a, int& b, int& c) {
+  a = bin_axis(g, 0, p[0]);
+  b = bin_axis(g, 1, p[1]);
+  c = bin_axis(g, 2, p[2]);
+}
+
 // The voxel centre as the reference forms it in float (RayTracingEngine.hpp:157, :66):
 // centroid = f32(f64(x) + delta/2) of a voxel's corner x ...
 __host__ __device__ inline void centre_of_corner(const Geom& g, float x, float y, float z, float cen[3]) {

@@ -145,7 +145,7 @@ int compact_masks(dmf_volume* v, const uint64_t* d_masks, int P, int64_t words, 
                   int64_t* counts_h, uint64_t** d_out_lists, int64_t* total, int value_kind);
 enum { kValueSlotHash = 0, kValueEnumCentroidHash = 1 };
 
-// greedySetCover (Algorithms.hpp:38-86) over P device bitmasks of `words` uint64 (dmf_trace.hip);
+// greedySetCover (Algorithms.hpp:38-86) over P device bitmasks of `words` uint64 (dmf_cover.hip);
 // the selection order comes back on the host.  Scratch: kScTmp and kScCount.
 int greedy_cover(dmf_volume* v, const uint64_t* d_masks, int P, int64_t words, int min_gain, int32_t* selected,
                  int32_t* nselected);

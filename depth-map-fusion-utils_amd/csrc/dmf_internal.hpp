@@ -55,6 +55,16 @@ __device__ inline float div_rn(float n, float d, float y) {
   return fmaf(r, y, q0);
 }
 
+// One sample of a 1 mm march from c along v: pt = c + (v * (float)depth) / 1000.0f per axis
+// (Eigen evaluates the double depth as float; RayTracingEngine.hpp:82, :173; the planner's
+// willCollide, tests/CameraPathGen.cpp:140, forms its samples the same way).
+__device__ inline void march_sample(const float cen[3], const float v[3], int depth, float p[3]) {
+  const float fd = (float)depth;
+  p[0] = cen[0] + div_rn(v[0] * fd, 1000.0f, 1.0f / 1000.0f);
+  p[1] = cen[1] + div_rn(v[1] * fd, 1000.0f, 1.0f / 1000.0f);
+  p[2] = cen[2] + div_rn(v[2] * fd, 1000.0f, 1.0f / 1000.0f);
+}
+
 // Forward (camera->world) pose and its Eigen Affine inverse, row-major 3x4.
 struct PoseX {
   float f[12];
@@ -115,6 +125,13 @@ __device__ inline bool deproject_valid(const CamP& c, float x, float y, float z,
 __device__ inline bool valid_points(const Geom& g, float x, float y, float z) {
   return !((double)x >= g.mx[0] || (double)y >= g.mx[1] || (double)z >= g.mx[2] ||
            (double)x <= g.mn[0] || (double)y <= g.mn[1] || (double)z <= g.mn[2]);
+}
+
+// The same test as exact float compares vlo <= x <= vhi (Geom): one combined mask, no per-axis
+// branches
+__device__ inline bool valid_points_f(const Geom& g, const float p[3]) {
+  return (p[0] >= g.vlo[0]) & (p[0] <= g.vhi[0]) & (p[1] >= g.vlo[1]) & (p[1] <= g.vhi[1]) & (p[2] >= g.vlo[2]) &
+         (p[2] <= g.vhi[2]);
 }
 
 // Volume.hpp:167-170 validCoords

@@ -7,8 +7,9 @@
 //  * forward depth-plane march (rayTrace* :229-494): one lane per lattice pixel,
 //    first occupied sample per pixel; list outputs are ordered by the reference
 //    loop key (z_depth, r, c) through a per-voxel atomicMin + radix sort.
-//  * z-buffer splat rayTraceVolume (:498-564) and the willCollide segment march
-//    (tests/CameraPathGen.cpp:128-156).
+//  * z-buffer splat rayTraceVolume (:498-564).
+// (The greedy set cover over the reverse march's masks is dmf_cover.hip, the planner's
+// willCollide and cost map dmf_collide.hip.)
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -47,13 +48,33 @@ __device__ inline void wave_add_u64(unsigned long long* dst, unsigned long long 
   if ((threadIdx.x & 63) == 0 && x) atomicAdd(dst, x);
 }
 
-// One sample of the reverse march: pt = c + (v * (float)depth) / 1000.0f per axis
-// (Eigen evaluates the double depth as float; RayTracingEngine.hpp:82, :173).
-__device__ inline void march_sample(const float cen[3], const float v[3], int depth, float p[3]) {
-  const float fd = (float)depth;
-  p[0] = cen[0] + div_rn(v[0] * fd, 1000.0f, 1.0f / 1000.0f);
-  p[1] = cen[1] + div_rn(v[1] * fd, 1000.0f, 1.0f / 1000.0f);
-  p[2] = cen[2] + div_rn(v[2] * fd, 1000.0f, 1.0f / 1000.0f);
+// Element e of a reverse march's list -> the voxel's centre; returns its slot.
+// kEnum = false: reverseRayTraceFast over occupied_cells_ (e = the slot)
+// kEnum = true : reverseRayTrace over the float-accumulated enumeration list
+template <bool kEnum>
+__device__ inline int64_t rev_item(const Geom& g, const DevVol& vd, const EnumList& el, int64_t e, float cen[3]) {
+  if (!kEnum) {
+    const uint64_t h = vd.hash[e];
+    const int xid = (int)(h >> 40), yid = (int)((h >> 20) & 0xFFFFF), zid = (int)(h & 0xFFFFF);
+    cell_centre(g, xid, yid, zid, cen);
+    return e;
+  }
+  float x, y, z;
+  enum_xyz(el.axes, el.nax, el.list[e], &x, &y, &z);
+  const int32_t slot = vd.slot_of[lin_index(g, bin_axis(g, 0, x), bin_axis(g, 1, y), bin_axis(g, 2, z))];
+  centre_of_corner(g, x, y, z, cen);
+  return slot;
+}
+
+// "Some point of the slot carries a normal within 90 degrees of v" (RayTracingEngine.hpp:205-215)
+__device__ inline bool slot_faces(const DevVol& vd, int64_t slot, const float v[3], float dstar) {
+  bool faces = false;
+  const int32_t a = vd.off[slot], b = vd.off[slot + 1];
+  for (int32_t j = a; j < b; ++j) {
+    const float4 n = vd.nrm[j];
+    if (n.w != 0.0f && angle_ok(n.x, n.y, n.z, v, dstar)) { faces = true; break; }
+  }
+  return faces;
 }
 
 // The reverse 1 mm march (RayTracingEngine.hpp:81-103 / :172-200).  Returns true if
@@ -125,8 +146,7 @@ __device__ inline bool reverse_march(const Geom& g, const DevVol& vd, const floa
   return true;
 }
 
-// kEnum = false: reverseRayTraceFast over occupied_cells_ (element = slot)
-// kEnum = true : reverseRayTrace over the float-accumulated enumeration list
+// One lane per element of the list (rev_item) and pose.
 template <bool kEnum, bool kSkip>
 __global__ __launch_bounds__(256) void k_reverse(Geom g, DevVol vd, CamP cam, const PoseX* __restrict__ poses,
                                                  int64_t nelem, EnumList el, int depth0, int max_steps, float dstar,
@@ -141,18 +161,7 @@ __global__ __launch_bounds__(256) void k_reverse(Geom g, DevVol vd, CamP cam, co
   int64_t samples = 0;
   if (e < nelem) {
     float cen[3];
-    int64_t slot;
-    if (!kEnum) {
-      slot = e;
-      const uint64_t h = vd.hash[e];
-      const int xid = (int)(h >> 40), yid = (int)((h >> 20) & 0xFFFFF), zid = (int)(h & 0xFFFFF);
-      cell_centre(g, xid, yid, zid, cen);
-    } else {
-      float x, y, z;
-      enum_xyz(el.axes, el.nax, el.list[e], &x, &y, &z);
-      slot = vd.slot_of[lin_index(g, bin_axis(g, 0, x), bin_axis(g, 1, y), bin_axis(g, 2, z))];
-      centre_of_corner(g, x, y, z, cen);
-    }
+    const int64_t slot = rev_item<kEnum>(g, vd, el, e, cen);
     const PoseX& T = poses[p];
     float t[3];
     xform(T.i, cen[0], cen[1], cen[2], t);
@@ -168,17 +177,7 @@ __global__ __launch_bounds__(256) void k_reverse(Geom g, DevVol vd, CamP cam, co
       if (!collided) {
         vis = true;
         const double zz = (double)t[2];
-        if (zz >= kZMin && zz <= kZMax) {
-          if (normal_test) {
-            const int32_t a = vd.off[slot], b = vd.off[slot + 1];
-            for (int32_t j = a; j < b; ++j) {
-              const float4 n = vd.nrm[j];
-              if (n.w != 0.0f && angle_ok(n.x, n.y, n.z, v, dstar)) { good = true; break; }
-            }
-          } else {
-            good = true;
-          }
-        }
+        if (zz >= kZMin && zz <= kZMax) good = !normal_test || slot_faces(vd, slot, v, dstar);
       }
     }
     if (viz) {
@@ -219,22 +218,6 @@ struct RevLane {
   float pn[3];          // sample pns, computed ahead
   int pns;
 };
-
-__device__ inline bool valid_points_f(const Geom& g, const float p[3]) {
-  // one combined mask (no per-axis branches)
-  return (p[0] >= g.vlo[0]) & (p[0] <= g.vhi[0]) & (p[1] >= g.vlo[1]) & (p[1] <= g.vhi[1]) & (p[2] >= g.vlo[2]) &
-         (p[2] <= g.vhi[2]);
-}
-
-// getVoxel of a point inside the volume in the reference's double arithmetic (bin_axis).
-// (The certified float bins of dmf_geom.hpp bin_axis_f, exact by tools/binning_selftest.cpp,
-// measured SLOWER in the reverse march: 8.35 vs 7.57 ms per 128-pose batch -- gfx950 runs
-// the fp64 add / mul / floor / converts at the non-packed fp32 rate)
-__device__ inline void bin_point(const Geom& g, const float p[3], int& a, int& b, int& c) {
-  a = bin_axis(g, 0, p[0]);
-  b = bin_axis(g, 1, p[1]);
-  c = bin_axis(g, 2, p[2]);
-}
 
 // Diagnostic build (DMF_EXP_STATS): sample categories into stats[2..12]
 #if defined(DMF_EXP_STATS)
@@ -357,18 +340,8 @@ __device__ inline bool rev_wave(const Geom& g, const DevVol& vd, const CamP& cam
           const int64_t e = base + it;
           ++rays;
           float cen[3];
-          int32_t slot;
-          if (!kEnum) {
-            slot = kOrder ? (int32_t)order[e] : (int32_t)e;
-            const uint64_t h = vd.hash[slot];
-            const int xid = (int)(h >> 40), yid = (int)((h >> 20) & 0xFFFFF), zid = (int)(h & 0xFFFFF);
-            cell_centre(g, xid, yid, zid, cen);
-          } else {
-            float x, y, z;
-            enum_xyz(el.axes, el.nax, el.list[e], &x, &y, &z);
-            slot = vd.slot_of[lin_index(g, bin_axis(g, 0, x), bin_axis(g, 1, y), bin_axis(g, 2, z))];
-            centre_of_corner(g, x, y, z, cen);
-          }
+          // (spatial order: item e of the wave's queue is the voxel of slot order[e])
+          const int32_t slot = (int32_t)rev_item<kEnum>(g, vd, el, kOrder ? (int32_t)order[e] : e, cen);
           float t[3];
           xform(T.i, cen[0], cen[1], cen[2], t);
           int r, c;
@@ -418,17 +391,7 @@ __device__ inline bool rev_wave(const Geom& g, const DevVol& vd, const CamP& cam
         any_vis = true;
         bool good = false;
         const double zz = (double)L.tz;
-        if (zz >= kZMin && zz <= kZMax) {
-          if (normal_test) {
-            const int32_t a = vd.off[L.slot], b = vd.off[L.slot + 1];
-            for (int32_t j = a; j < b; ++j) {
-              const float4 n = vd.nrm[j];
-              if (n.w != 0.0f && angle_ok(n.x, n.y, n.z, L.v, dstar)) { good = true; break; }
-            }
-          } else {
-            good = true;
-          }
-        }
+        if (zz >= kZMin && zz <= kZMax) good = !normal_test || slot_faces(vd, L.slot, L.v, dstar);
         atomicOr(&lvis[L.item >> 5], 1u << (L.item & 31));
         if (good) atomicOr(&lgood[L.item >> 5], 1u << (L.item & 31));
         if (viz) {
@@ -440,6 +403,21 @@ __device__ inline bool rev_wave(const Geom& g, const DevVol& vd, const CamP& cam
     }
   }
   return any_vis;
+}
+
+// The end of a queue kernel: each wave adds its capped marches to the hazards and its counters
+// to the statistics.
+__device__ inline void rev_finish(unsigned long long ncap, int64_t samples, int64_t rays, const unsigned long long* rst,
+                                  unsigned long long* hazards, unsigned long long* stats) {
+  wave_add_u64(hazards, ncap);
+  if (stats) {
+    wave_add_u64(&stats[0], (unsigned long long)samples);
+    wave_add_u64(&stats[1], (unsigned long long)rays);
+#if defined(DMF_EXP_STATS)
+#pragma unroll
+    for (int i = 0; i < kRevStatN; ++i) wave_add_u64(&stats[2 + i], rst[i]);
+#endif
+  }
 }
 
 template <bool kEnum, int kItems, int kRefill, int kBurst, bool kOrder = false>
@@ -476,16 +454,7 @@ __global__ __launch_bounds__(256) void k_reverse_q(Geom g, DevVol vd, CamP cam, 
     }
   }
   if (__builtin_amdgcn_ballot_w64(any_vis) != 0 && l == 0) atomicOr(&found[p], 1);
-  for (int o = 32; o > 0; o >>= 1) ncap += __shfl_down(ncap, o, 64);
-  if (l == 0 && ncap) atomicAdd(hazards, ncap);
-  if (stats) {
-    wave_add_u64(&stats[0], (unsigned long long)samples);
-    wave_add_u64(&stats[1], (unsigned long long)rays);
-#if defined(DMF_EXP_STATS)
-#pragma unroll
-    for (int i = 0; i < kRevStatN; ++i) wave_add_u64(&stats[2 + i], rst[i]);
-#endif
-  }
+  rev_finish(ncap, samples, rays, rst, hazards, stats);
 }
 
 // reverseRayTraceFast with per-XCD work queues (spatial order only).  A unit is one wave's
@@ -556,16 +525,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kRevWaves))
       if (__builtin_amdgcn_ballot_w64(any_vis) != 0 && l == 0) atomicOr(&found[p], 1);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) ncap += __shfl_down(ncap, o, 64);
-  if (l == 0 && ncap) atomicAdd(hazards, ncap);
-  if (stats) {
-    wave_add_u64(&stats[0], (unsigned long long)samples);
-    wave_add_u64(&stats[1], (unsigned long long)rays);
-#if defined(DMF_EXP_STATS)
-#pragma unroll
-    for (int i = 0; i < kRevStatN; ++i) wave_add_u64(&stats[2 + i], rst[i]);
-#endif
-  }
+  rev_finish(ncap, samples, rays, rst, hazards, stats);
 }
 
 // Item-ordered result bits (k_reverse_q<*, kOrder>) -> occupied_cells_ order: one wave per
@@ -646,120 +606,6 @@ static int ensure_spatial_order(dmf_volume* v) {
   return DMF_OK;
 }
 
-// ---- greedy set cover over per-pose good bitmasks (Algorithms.hpp:38-86) ---------
-// The reference scans the remaining set ids in increasing order and keeps the
-// strictly largest |set \ covered|; with sets as bitmasks over occupied slots that
-// difference size is popcount(good[p] & ~covered).  One iteration = gain, pick,
-// merge; every kernel returns at once after the stop condition.
-struct CoverCtl {
-  int done;
-  int sel;
-  int nsel;
-};
-
-__global__ __launch_bounds__(256) void k_cover_gain(const uint64_t* __restrict__ masks, int64_t words,
-                                                    const uint64_t* __restrict__ covered,
-                                                    const uint8_t* __restrict__ removed,
-                                                    unsigned long long* __restrict__ gain,
-                                                    const CoverCtl* __restrict__ ctl) {
-  if (ctl->done) return;
-  const int p = blockIdx.x;
-  if (removed[p]) {
-    if (threadIdx.x == 0) gain[p] = 0;
-    return;
-  }
-  const uint64_t* m = masks + (int64_t)p * words;
-  unsigned long long c = 0;
-  for (int64_t w = threadIdx.x; w < words; w += blockDim.x) c += __popcll(m[w] & ~covered[w]);
-  __shared__ unsigned long long part[4];
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) gain[p] = part[0] + part[1] + part[2] + part[3];
-}
-
-// The pick's order: the larger gain, and among equal gains the smaller index.
-__device__ __forceinline__ bool cover_better(unsigned long long g, int p, unsigned long long bg, int bp) {
-  return g > bg || (g == bg && p < bp);
-}
-
-__global__ __launch_bounds__(256) void k_cover_pick(const unsigned long long* __restrict__ gain, int P, int min_gain,
-                                                    uint8_t* __restrict__ removed, int32_t* __restrict__ selected,
-                                                    CoverCtl* __restrict__ ctl) {
-  if (ctl->done) return;
-  // argmax with ties to the smallest index, over the pair (gain, index): the gain keeps all its
-  // 64 bits (up to 64 * words), so the two do not share one key
-  unsigned long long g = 0;
-  int p = P;
-  for (int q = threadIdx.x; q < P; q += blockDim.x)
-    if (cover_better(gain[q], q, g, p)) { g = gain[q]; p = q; }
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long tg = __shfl_down(g, o, 64);
-    const int tp = __shfl_down(p, o, 64);
-    if (cover_better(tg, tp, g, p)) { g = tg; p = tp; }
-  }
-  __shared__ unsigned long long part_g[4];
-  __shared__ int part_p[4];
-  if ((threadIdx.x & 63) == 0) { part_g[threadIdx.x >> 6] = g; part_p[threadIdx.x >> 6] = p; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < 4; ++i)
-      if (cover_better(part_g[i], part_p[i], g, p)) { g = part_g[i]; p = part_p[i]; }
-    // selected == -1, or max_points < 5 (a signed compare: min_gain <= 0 stops at "adds nothing" alone)
-    if (g == 0 || (min_gain > 0 && g < (unsigned long long)min_gain)) {
-      ctl->done = 1;
-    } else {
-      ctl->sel = p;
-      selected[ctl->nsel++] = p;
-      removed[p] = 1;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_cover_merge(const uint64_t* __restrict__ masks, int64_t words,
-                                                     uint64_t* __restrict__ covered, const CoverCtl* __restrict__ ctl) {
-  if (ctl->done) return;
-  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w < words) covered[w] |= masks[(int64_t)ctl->sel * words + w];
-}
-
-int greedy_cover(dmf_volume* v, const uint64_t* d_masks, int P, int64_t words, int min_gain, int32_t* selected,
-                 int32_t* nselected) {
-  if (P <= 0) { *nselected = 0; return DMF_OK; }
-  void *cov, *aux;
-  const size_t cov_bytes = sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1);
-  DMF_TRY(scratch(v, kScTmp, cov_bytes, &cov));
-  const size_t gain_off = 64, rem_off = gain_off + sizeof(unsigned long long) * P,
-               sel_off = rem_off + ((size_t)P + 7) / 8 * 8;
-  DMF_TRY(scratch(v, kScCount, sel_off + sizeof(int32_t) * P, &aux));
-  CoverCtl* ctl = (CoverCtl*)aux;
-  unsigned long long* gain = (unsigned long long*)((char*)aux + gain_off);
-  uint8_t* removed = (uint8_t*)aux + rem_off;
-  int32_t* sel = (int32_t*)((char*)aux + sel_off);
-  DMF_HIP(hipMemsetAsync(cov, 0, cov_bytes, v->stream));
-  DMF_HIP(hipMemsetAsync(aux, 0, sel_off, v->stream));
-  const unsigned mb = (unsigned)((words + 255) / 256);
-  for (int it = 0; it < P; it += 8) {
-    for (int k = it; k < std::min(P, it + 8); ++k) {
-      hipLaunchKernelGGL(k_cover_gain, dim3((unsigned)P), dim3(256), 0, v->stream, d_masks, words,
-                         (const uint64_t*)cov, removed, gain, ctl);
-      hipLaunchKernelGGL(k_cover_pick, dim3(1), dim3(256), 0, v->stream, gain, P, min_gain, removed, sel, ctl);
-      if (mb) hipLaunchKernelGGL(k_cover_merge, dim3(mb), dim3(256), 0, v->stream, d_masks, words, (uint64_t*)cov, ctl);
-    }
-    DMF_LAUNCH_CHECK();
-    CoverCtl h;
-    DMF_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, v->stream));
-    DMF_HIP(hipStreamSynchronize(v->stream));
-    if (h.done) break;
-  }
-  CoverCtl h;
-  DMF_HIP(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, v->stream));
-  DMF_HIP(hipStreamSynchronize(v->stream));
-  if (h.nsel) DMF_HIP(hipMemcpy(selected, sel, sizeof(int32_t) * h.nsel, hipMemcpyDeviceToHost));
-  *nselected = h.nsel;
-  return DMF_OK;
-}
-
 static int max_march_steps(const dmf_volume* v) {
   const double dx = v->xmax - v->xmin, dy = v->ymax - v->ymin, dz = v->zmax - v->zmin;
   const double diag_mm = std::sqrt(dx * dx + dy * dy + dz * dz) * 1000.0;
@@ -817,18 +663,10 @@ static int run_reverse(dmf_volume* v, const dmf_camera* cam, const float* poses,
     const CamP cp = cam_params(cam);
     const int ms = max_march_steps(v);
     if (kr == 1 || kr == 2) {
-      const bool skip = kr == 2;
-      if (enumerate) {
-        if (skip) hipLaunchKernelGGL((k_reverse<true, true>), grid, dim3(256), 0, v->stream, g, dv, cp, tab, nelem, el,
-                                     depth0, ms, v->dstar, viz, 0, vis, good, words, st, found, hz);
-        else hipLaunchKernelGGL((k_reverse<true, false>), grid, dim3(256), 0, v->stream, g, dv, cp, tab, nelem, el,
-                                depth0, ms, v->dstar, viz, 0, vis, good, words, st, found, hz);
-      } else {
-        if (skip) hipLaunchKernelGGL((k_reverse<false, true>), grid, dim3(256), 0, v->stream, g, dv, cp, tab, nelem,
-                                     el, depth0, ms, v->dstar, viz, 1, vis, good, words, st, found, hz);
-        else hipLaunchKernelGGL((k_reverse<false, false>), grid, dim3(256), 0, v->stream, g, dv, cp, tab, nelem, el,
-                                depth0, ms, v->dstar, viz, 1, vis, good, words, st, found, hz);
-      }
+      const auto kfn = enumerate ? (kr == 2 ? k_reverse<true, true> : k_reverse<true, false>)
+                                 : (kr == 2 ? k_reverse<false, true> : k_reverse<false, false>);
+      hipLaunchKernelGGL(kfn, grid, dim3(256), 0, v->stream, g, dv, cp, tab, nelem, el, depth0, ms, v->dstar, viz,
+                         enumerate ? 0 : 1, vis, good, words, st, found, hz);
     } else {
       DMF_TRY(ensure_brick_dist(v));
       // the queue kernel writes every mask word it owns; words past the last wave stay 0
@@ -853,22 +691,16 @@ static int run_reverse(dmf_volume* v, const dmf_camera* cam, const float* poses,
           // L2 requests x1.6).  DESIGN.md §5.5, profiles/r05b/
           unsigned int* heads = (unsigned int*)(good_i + P * words);
           DMF_HIP(hipMemsetAsync(heads, 0, 8 * sizeof(unsigned int), v->stream));
-          const bool wg_units = kr != 4;
-          const void* kfn = wg_units ? (const void*)k_reverse_x<kSpItems, kSpRefill, kSpBurst, true>
-                                     : (const void*)k_reverse_x<kSpItems, kSpRefill, kSpBurst, false>;
+          const auto kfn = kr != 4 ? k_reverse_x<kSpItems, kSpRefill, kSpBurst, true>
+                                   : k_reverse_x<kSpItems, kSpRefill, kSpBurst, false>;
           int per_cu = 0;
-          DMF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, 0));
+          DMF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kfn, 256, 0));
           int ncu = 0;
           DMF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, v->device));
           const unsigned nwg = (unsigned)(std::max(ncu, 8) * std::max(per_cu, 1));
-          if (wg_units)
-            hipLaunchKernelGGL((k_reverse_x<kSpItems, kSpRefill, kSpBurst, true>), dim3(nwg), dim3(256), 0, v->stream, g,
-                               dv, cp, tab, P, nelem, (const uint32_t*)v->d_sorder, depth0, ms, v->dstar, viz, vis_i,
-                               good_i, words, heads, st, found, hz);
-          else
-            hipLaunchKernelGGL((k_reverse_x<kSpItems, kSpRefill, kSpBurst, false>), dim3(nwg), dim3(256), 0, v->stream,
-                               g, dv, cp, tab, P, nelem, (const uint32_t*)v->d_sorder, depth0, ms, v->dstar, viz, vis_i,
-                               good_i, words, heads, st, found, hz);
+          hipLaunchKernelGGL(kfn, dim3(nwg), dim3(256), 0, v->stream, g, dv, cp, tab, P, nelem,
+                             (const uint32_t*)v->d_sorder, depth0, ms, v->dstar, viz, vis_i, good_i, words, heads, st,
+                             found, hz);
         } else {
           hipLaunchKernelGGL((k_reverse_q<false, kSpItems, kSpRefill, kSpBurst, true>), gridqs, dim3(256), 0, v->stream, g,
                              dv, cp, tab, nelem, el, (const uint32_t*)v->d_sorder, depth0, ms, v->dstar, viz, 1, vis_i,
@@ -1359,24 +1191,22 @@ __global__ __launch_bounds__(256) void k_forward_x(Geom g, DevVol vd, CamP cam, 
 // k_forward_q's shape: tiles per wave unit, refill threshold, samples per burst
 constexpr int kFwdUnit = 4, kFwdRefill = 16, kFwdBurst = 8;
 
-// threads of a k_forward launch per pose: whole 8x8 tiles of the R x C lattice
-static unsigned fwd_blocks(int R, int C) {
-  const int64_t threads = (int64_t)((R + 7) / 8) * ((C + 7) / 8) * 64;
-  return (unsigned)((threads + 255) / 256);
-}
-
 // DMF_KNOB_FWD_SKIP = -1 (dmf_diag.h) disables the forward march's empty-space skipping (A/B)
 static bool fwd_skip(const dmf_volume* v) { return v->knob[DMF_KNOB_FWD_SKIP] >= 0; }
 
-#define DMF_LAUNCH_FORWARD(GRID, ...)                                                                          \
-  do {                                                                                                        \
-    if (fwd_skip(v)) {                                                                                         \
-      DMF_TRY(ensure_brick_dist(v));                                                                          \
-      hipLaunchKernelGGL(k_forward<true>, GRID, dim3(256), 0, v->stream, __VA_ARGS__);                         \
-    } else {                                                                                                  \
-      hipLaunchKernelGGL(k_forward<false>, GRID, dim3(256), 0, v->stream, __VA_ARGS__);                        \
-    }                                                                                                         \
-  } while (0)
+// Launches k_forward over the R x C lattice of P poses: whole 8x8 tiles per pose, 4 to a workgroup.
+// The caller checks the launch.
+static int launch_forward(dmf_volume* v, const dmf_camera* cam, const PoseX* tab, int P, int zstart, int zdelta,
+                          int rdelta, int cdelta, int R, int C, int32_t* k_out, int32_t* slot_out,
+                          unsigned long long* hazards, unsigned long long* stats) {
+  const int64_t threads = (int64_t)((R + 7) / 8) * ((C + 7) / 8) * 64;
+  const dim3 grid((unsigned)((threads + 255) / 256), (unsigned)P);
+  const bool skip = fwd_skip(v);
+  if (skip) DMF_TRY(ensure_brick_dist(v));
+  hipLaunchKernelGGL(skip ? k_forward<true> : k_forward<false>, grid, dim3(256), 0, v->stream, v->geom(), v->dev(),
+                     cam_params(cam), tab, zstart, zdelta, rdelta, cdelta, R, C, k_out, slot_out, hazards, stats);
+  return DMF_OK;
+}
 
 enum FwdMode { kTrace = 0, kClassify = 1, kGoodPoints = 2, kPoints = 3, kMinimum = 4 };
 
@@ -1417,14 +1247,7 @@ __global__ void k_forward_post(Geom g, DevVol vd, CamP cam, const PoseX* __restr
   const float d[3] = {pose->f[3] - cen[0], pose->f[7] - cen[1], pose->f[11] - cen[2]};
   float v[3];
   normalized(d, v);
-  bool ok = false;
-  if (zd >= 250 && zd <= 600) {
-    const int32_t a = vd.off[slot], b = vd.off[slot + 1];
-    for (int32_t j = a; j < b; ++j) {
-      const float4 n = vd.nrm[j];
-      if (n.w != 0.0f && angle_ok(n.x, n.y, n.z, v, dstar)) { ok = true; break; }
-    }
-  }
+  const bool ok = zd >= 250 && zd <= 600 && slot_faces(vd, slot, v, dstar);
   if (mode == kClassify) {
     if (vd.view[slot] == 0) vd.view[slot] = view_arg;
     if (ok) vd.good[slot] = 1;
@@ -1478,8 +1301,8 @@ static int run_forward(dmf_volume* v, const dmf_camera* cam, const float* pose, 
   const CamP cp = cam_params(cam);
   const Geom g = v->geom();
   const dim3 grid((unsigned)((RC + 255) / 256));
-  DMF_LAUNCH_FORWARD(dim3(fwd_blocks(R, C)), g, v->dev(), cp, tab, zstart, zdelta, rdelta, cdelta, R, C, (int32_t*)kb, (int32_t*)sb, hz,
-                     nullptr);
+  DMF_TRY(launch_forward(v, cam, tab, 1, zstart, zdelta, rdelta, cdelta, R, C, (int32_t*)kb, (int32_t*)sb, hz,
+                         nullptr));
   DMF_LAUNCH_CHECK();
   unsigned long long* minkey = nullptr;
   if ((mode == kPoints || mode == kGoodPoints) && v->V > 0) {
@@ -1584,100 +1407,6 @@ __global__ void k_zbuf_out(const int* __restrict__ z, int64_t n, int* __restrict
   if (i < n) out[i] = z[i] == 0x7fffffff ? -1 : z[i];
 }
 
-// ---------------------------------------------------------------- willCollide
-// tests/CameraPathGen.cpp:128-156, one lane per segment.
-__global__ void k_will_collide(Geom g, const uint32_t* __restrict__ occ, const float* __restrict__ A,
-                               const float* __restrict__ B, int64_t n, uint8_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float a[3] = {A[3 * i], A[3 * i + 1], A[3 * i + 2]};
-  const float b[3] = {B[3 * i], B[3 * i + 1], B[3 * i + 2]};
-  const float ab[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
-  const double distance = (double)sqrtf(sum3(ab[0] * ab[0], ab[1] * ab[1], ab[2] * ab[2]));
-  const float ba[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
-  float v[3];
-  normalized(ba, v);
-  bool collided = false;
-  const double lim = distance * 1000;
-  for (int depth = 1; !collided; depth++) {
-    if ((double)depth > lim) break;
-    const float fd = (float)depth;
-    const float px = a[0] + div_rn(v[0] * fd, 1000.0f, 1.0f / 1000.0f);
-    const float py = a[1] + div_rn(v[1] * fd, 1000.0f, 1.0f / 1000.0f);
-    const float pz = a[2] + div_rn(v[2] * fd, 1000.0f, 1.0f / 1000.0f);
-    const float pp[3] = {px, py, pz};
-    if (!valid_points_f(g, pp)) continue;
-    int x, y, z;
-    bin_point(g, pp, x, y, z);
-    if (!valid_coords(g, x, y, z)) continue;
-    if (occ_test(occ, occ_bit(g, x, y, z))) collided = true;
-  }
-  out[i] = collided ? 1 : 0;
-}
-
-// Planner::run_tsp cost map (tests/CameraPathGen.cpp:310-331): all V*V ordered pairs
-// of camera centres, map = INT_MAX if willCollide(a, b) else int(|a-b| * 1000).
-// willCollide's loop only ever sets `collided`, so its result is the OR over depths
-// 1..floor(distance*1000) of "sample valid and occupied": one wave per pair, lane l
-// tests depth base+l, a ballot ends the pair at the first occupied 64-depth group.
-// Every lane evaluates the same float expressions as the scalar loop, so the OR is
-// bit-identical to the sequential march and there is no per-lane length divergence.
-// Pairs whose segment the reference cannot march (non-finite, or more than INT_MAX
-// depths: the int counter overflows) get -1.
-constexpr int kCostWaves = 4;
-constexpr int32_t kMaxCostPoses = 46340;  // V*V int32 entries < 2^31
-__global__ __launch_bounds__(64 * kCostWaves) void k_cost_map(Geom g, const uint32_t* __restrict__ occ,
-                                                              const float* __restrict__ poses, int32_t V,
-                                                              int32_t* __restrict__ map) {
-  const int64_t pair = (int64_t)blockIdx.x * kCostWaves + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (pair >= (int64_t)V * V) return;
-  const int64_t i = pair / V, j = pair - i * V;
-  const float a[3] = {poses[12 * i + 3], poses[12 * i + 7], poses[12 * i + 11]};
-  const float b[3] = {poses[12 * j + 3], poses[12 * j + 7], poses[12 * j + 11]};
-  const float ab[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
-  const double distance = (double)sqrtf(sum3(ab[0] * ab[0], ab[1] * ab[1], ab[2] * ab[2]));
-  const double lim = distance * 1000;
-  if (!(lim < 2147483647.0)) {  // NaN or an overflowing depth counter
-    if (lane == 0) map[pair] = -1;
-    return;
-  }
-  const float ba[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
-  float v[3];
-  normalized(ba, v);
-  bool collided = false;
-  for (int64_t base = 1; (double)base <= lim; base += 64) {
-    const int64_t depth = base + lane;
-    bool hit = false;
-    if ((double)depth <= lim) {
-      const float fd = (float)depth;
-      const float px = a[0] + div_rn(v[0] * fd, 1000.0f, 1.0f / 1000.0f);
-      const float py = a[1] + div_rn(v[1] * fd, 1000.0f, 1.0f / 1000.0f);
-      const float pz = a[2] + div_rn(v[2] * fd, 1000.0f, 1.0f / 1000.0f);
-      const float pp[3] = {px, py, pz};
-      if (valid_points_f(g, pp)) {
-        int x, y, z;
-        bin_point(g, pp, x, y, z);
-        hit = valid_coords(g, x, y, z) && occ_test(occ, occ_bit(g, x, y, z));
-      }
-    }
-    if (__builtin_amdgcn_ballot_w64(hit)) {
-      collided = true;
-      break;
-    }
-  }
-  if (lane == 0) map[pair] = collided ? 0x7fffffff : to_int_x86(distance * 1000);
-}
-
-static int cost_map(dmf_volume* v, const float* d_poses, int32_t V, int32_t* d_map) {
-  const int64_t pairs = (int64_t)V * V;
-  if (pairs == 0) return DMF_OK;
-  hipLaunchKernelGGL(k_cost_map, dim3((unsigned)((pairs + kCostWaves - 1) / kCostWaves)), dim3(64 * kCostWaves), 0,
-                     v->stream, v->geom(), v->d_occ, d_poses, V, d_map);
-  DMF_LAUNCH_CHECK();
-  return DMF_OK;
-}
-
 }  // namespace dmf
 
 using namespace dmf;
@@ -1710,16 +1439,6 @@ int dmf_reverse_visibility_device(dmf_volume* v, const dmf_camera* cam, const fl
     if (d_good) DMF_HIP(hipMemcpyAsync(d_good, good, bytes, hipMemcpyDeviceToDevice, v->stream));
   }
   return DMF_OK;
-  DMF_API_END
-}
-
-int dmf_greedy_set_cover_masks_device(dmf_volume* v, const uint64_t* d_masks, int32_t P, int64_t words,
-                                      int32_t min_gain, int32_t* selected, int32_t* nselected) {
-  DMF_API_BEGIN
-  DMF_TRY(require_constructed(v));
-  if (!selected || !nselected || (P > 0 && !d_masks)) return fail(DMF_ERR_INVALID, "null argument");
-  if (P < 0 || P > 65535 || words < 0) return fail(DMF_ERR_INVALID, "bad set count / width");
-  return greedy_cover(v, d_masks, P, words, min_gain, selected, nselected);
   DMF_API_END
 }
 
@@ -1805,34 +1524,26 @@ int dmf_forward_first_hits_device(dmf_volume* v, const dmf_camera* cam, const fl
     unsigned int* heads = (unsigned int*)aux + 8;
     const bool skip = fwd_skip(v);
     if (skip) DMF_TRY(ensure_brick_dist(v));
-    const void* kfn = skip ? (const void*)k_forward_x<true> : (const void*)k_forward_x<false>;
+    const auto kfn = skip ? k_forward_x<true> : k_forward_x<false>;
     int per_cu = 0, ncu = 0;
-    DMF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, 0));
+    DMF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kfn, 256, 0));
     DMF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, v->device));
     const dim3 grid((unsigned)(std::max(ncu, 8) * std::max(per_cu, 1)));
-    if (skip)
-      hipLaunchKernelGGL(k_forward_x<true>, grid, dim3(256), 0, v->stream, v->geom(), v->dev(), cam_params(cam), tab, P,
-                         zstart, zdelta, rdelta, cdelta, R, C, d_k, d_slot, heads, (unsigned long long*)aux, st);
-    else
-      hipLaunchKernelGGL(k_forward_x<false>, grid, dim3(256), 0, v->stream, v->geom(), v->dev(), cam_params(cam), tab,
-                         P, zstart, zdelta, rdelta, cdelta, R, C, d_k, d_slot, heads, (unsigned long long*)aux, st);
+    hipLaunchKernelGGL(kfn, grid, dim3(256), 0, v->stream, v->geom(), v->dev(), cam_params(cam), tab, P, zstart,
+                       zdelta, rdelta, cdelta, R, C, d_k, d_slot, heads, (unsigned long long*)aux, st);
   } else if (v->knob[DMF_KNOB_FWD_KERNEL] == 2) {
     // per-wave lane refill over units of kFwdUnit tiles (k_forward_q)
     const int64_t ntiles = (int64_t)((R + 7) / 8) * ((C + 7) / 8), nunits = (ntiles + kFwdUnit - 1) / kFwdUnit;
     const dim3 grid((unsigned)((nunits + 3) / 4), (unsigned)P);
-    if (fwd_skip(v)) {
-      DMF_TRY(ensure_brick_dist(v));
-      hipLaunchKernelGGL((k_forward_q<true, kFwdUnit, kFwdRefill, kFwdBurst>), grid, dim3(256), 0, v->stream, v->geom(),
-                         v->dev(), cam_params(cam), tab, zstart, zdelta, rdelta, cdelta, R, C, d_k, d_slot,
-                         (unsigned long long*)aux, st);
-    } else {
-      hipLaunchKernelGGL((k_forward_q<false, kFwdUnit, kFwdRefill, kFwdBurst>), grid, dim3(256), 0, v->stream,
-                         v->geom(), v->dev(), cam_params(cam), tab, zstart, zdelta, rdelta, cdelta, R, C, d_k, d_slot,
-                         (unsigned long long*)aux, st);
-    }
+    const bool skip = fwd_skip(v);
+    if (skip) DMF_TRY(ensure_brick_dist(v));
+    hipLaunchKernelGGL((skip ? k_forward_q<true, kFwdUnit, kFwdRefill, kFwdBurst>
+                             : k_forward_q<false, kFwdUnit, kFwdRefill, kFwdBurst>),
+                       grid, dim3(256), 0, v->stream, v->geom(), v->dev(), cam_params(cam), tab, zstart, zdelta, rdelta,
+                       cdelta, R, C, d_k, d_slot, (unsigned long long*)aux, st);
   } else {
-    DMF_LAUNCH_FORWARD(dim3(fwd_blocks(R, C), (unsigned)P), v->geom(), v->dev(), cam_params(cam), tab,
-                       zstart, zdelta, rdelta, cdelta, R, C, d_k, d_slot, (unsigned long long*)aux, st);
+    DMF_TRY(launch_forward(v, cam, tab, P, zstart, zdelta, rdelta, cdelta, R, C, d_k, d_slot,
+                           (unsigned long long*)aux, st));
   }
   DMF_LAUNCH_CHECK();
 #if defined(DMF_EXP_STATS)
@@ -1862,8 +1573,8 @@ int dmf_forward_first_hits(dmf_volume* v, const dmf_camera* cam, const float* po
   DMF_TRY(scratch(v, kScHost2, 64, &aux));
   DMF_HIP(hipMemsetAsync(aux, 0, 64, v->stream));
   const dim3 grid((unsigned)((RC + 255) / 256));
-  DMF_LAUNCH_FORWARD(dim3(fwd_blocks(R, C)), v->geom(), v->dev(), cam_params(cam), tab, zstart, zdelta, rdelta, cdelta, R, C,
-                     (int32_t*)kb, (int32_t*)sb, (unsigned long long*)aux, nullptr);
+  DMF_TRY(launch_forward(v, cam, tab, 1, zstart, zdelta, rdelta, cdelta, R, C, (int32_t*)kb, (int32_t*)sb,
+                         (unsigned long long*)aux, nullptr));
   DMF_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_first_hit_hash, grid, dim3(256), 0, v->stream, (const int32_t*)sb, v->d_hash, RC,
                      (uint64_t*)hb);
@@ -1912,58 +1623,6 @@ int dmf_ray_trace_volume(dmf_volume* v, const dmf_camera* cam, const float* pose
   DMF_HIP(hipStreamSynchronize(v->stream));
   v->hazards += (int64_t)hz + v->enum_hazards;
   return DMF_OK;
-  DMF_API_END
-}
-
-int dmf_will_collide(dmf_volume* v, const float* a, const float* b, int64_t n, uint8_t* collided) {
-  DMF_API_BEGIN
-  DMF_TRY(require_constructed(v));
-  if (n < 0 || (n > 0 && (!a || !b || !collided))) return fail(DMF_ERR_INVALID, "bad arguments");
-  if (n == 0) return DMF_OK;
-  for (int64_t i = 0; i < 3 * n; ++i)
-    if (!std::isfinite(a[i]) || !std::isfinite(b[i]))
-      return fail(DMF_ERR_INVALID, "non-finite segment endpoint (the reference never terminates)");
-  void *da, *db, *dout;
-  DMF_TRY(scratch(v, kScHost0, sizeof(float) * 3 * n, &da));
-  DMF_TRY(scratch(v, kScHost1, sizeof(float) * 3 * n, &db));
-  DMF_TRY(scratch(v, kScOut0, n, &dout));
-  DMF_HIP(hipMemcpyAsync(da, a, sizeof(float) * 3 * n, hipMemcpyHostToDevice, v->stream));
-  DMF_HIP(hipMemcpyAsync(db, b, sizeof(float) * 3 * n, hipMemcpyHostToDevice, v->stream));
-  hipLaunchKernelGGL(k_will_collide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, v->geom(), v->d_occ,
-                     (const float*)da, (const float*)db, n, (uint8_t*)dout);
-  DMF_LAUNCH_CHECK();
-  DMF_HIP(hipMemcpyAsync(collided, dout, n, hipMemcpyDeviceToHost, v->stream));
-  DMF_HIP(hipStreamSynchronize(v->stream));
-  return DMF_OK;
-  DMF_API_END
-}
-
-int dmf_collision_cost_map(dmf_volume* v, const float* poses, int32_t V, int32_t* map) {
-  DMF_API_BEGIN
-  DMF_TRY(require_constructed(v));
-  if (V < 0 || V > kMaxCostPoses || (V > 0 && (!poses || !map))) return fail(DMF_ERR_INVALID, "bad arguments");
-  if (V == 0) return DMF_OK;
-  for (int64_t i = 0; i < V; ++i)
-    for (int k = 3; k < 12; k += 4)
-      if (!std::isfinite(poses[12 * i + k]))
-        return fail(DMF_ERR_INVALID, "non-finite camera centre (the reference never terminates)");
-  const int64_t pairs = (int64_t)V * V;
-  void *dp, *dm;
-  DMF_TRY(scratch(v, kScPoses, sizeof(float) * 12 * V, &dp));
-  DMF_TRY(scratch(v, kScOut0, sizeof(int32_t) * pairs, &dm));
-  DMF_HIP(hipMemcpyAsync(dp, poses, sizeof(float) * 12 * V, hipMemcpyHostToDevice, v->stream));
-  DMF_TRY(cost_map(v, (const float*)dp, V, (int32_t*)dm));
-  DMF_HIP(hipMemcpyAsync(map, dm, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, v->stream));
-  DMF_HIP(hipStreamSynchronize(v->stream));
-  return DMF_OK;
-  DMF_API_END
-}
-
-int dmf_collision_cost_map_device(dmf_volume* v, const float* d_poses, int32_t V, int32_t* d_map) {
-  DMF_API_BEGIN
-  DMF_TRY(require_constructed(v));
-  if (V < 0 || V > kMaxCostPoses || (V > 0 && (!d_poses || !d_map))) return fail(DMF_ERR_INVALID, "bad arguments");
-  return cost_map(v, d_poses, V, d_map);
   DMF_API_END
 }
 

@@ -3,7 +3,7 @@
 // Cell classes of the int16 grid: solid (L >= occ), free (not solid, L <= free), unknown (neither).
 // Per pixel the ray-cast's own cell sequence (§4.1) up to its first solid cell; seen[p] = the
 // unknown cells of those stretches as a bitmask in the occupancy layout (dmf_gridbits.hpp), which
-// is what greedy_cover (dmf_trace.hip) takes.  Kernels:
+// is what greedy_cover (dmf_cover.hip) takes.  Kernels:
 //  k_vg_mask   — tile_mask_pass<2>: the solid and the unknown mask in one pass over the grid, and
 //                one word per workgroup of two tile levels: "holds a solid cell" and "holds a solid
 //                or an unknown cell" (not wholly free);

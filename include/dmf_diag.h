@@ -44,7 +44,8 @@ enum dmf_knob {
   DMF_KNOB_REVERSE_KERNEL = 7, /* reverseRayTraceFast march: 0 default (wave queues in spatial order + distance
                                   field, workgroup units from per-XCD queues: k_reverse_x), 1 plain, 2 plain +
                                   brick skip, 3 queue in insertion order, 4 per-XCD queues of wave units, 5 the
-                                  spatial-order queues on a (chunk, pose) grid (k_reverse_q) */
+                                  spatial-order queues on a (chunk, pose) grid (k_reverse_q); any other value is
+                                  DMF_ERR_INVALID */
   DMF_KNOB_FWD_SKIP = 8,    /* forward march empty-space skipping: 0 default (on), -1 off */
   DMF_KNOB_A_HASH = 9,      /* pass A's histogram: 0 default (hashed, 2048 words, above 8192 bricks; direct
                                below), -1 always direct, k > 0 always hashed with k words (rounded up to a
@@ -55,7 +56,7 @@ enum dmf_knob {
                                   buffers); 0 = off */
   DMF_KNOB_FWD_KERNEL = 11,  /* batched forward first hits (dmf_forward_first_hits_device): 0 default (a grid of
                                 (tile block, pose): k_forward), 1 per-XCD unit queues (k_forward_x), 2 per-wave lane refill
-                                over units of 8x8 tiles (k_forward_q) */
+                                over units of 8x8 tiles (k_forward_q); any other value is DMF_ERR_INVALID */
   DMF_KNOB_BDIST_CAP = 12,   /* saturation of the brick distance field of the reverse / forward marches' empty-space
                                 jumps, in bricks (1..255; 0 = the default 63); rebuilt at the next march */
   DMF_KNOB_RAYCAST_WALK = 13, /* log-odds ray-cast (dmf_raycast_logodds*): 0 default, 1 the masked cell-by-cell walk,

@@ -1,5 +1,5 @@
 """Packed-mask restatement of the greedy set cover (Algorithms.hpp:38-86; DESIGN.md §4.5;
-csrc/dmf_trace.hip: k_cover_gain, k_cover_pick, k_cover_merge) and the synthetic cases that reach
+csrc/dmf_cover.hip: k_cover_gain, k_cover_pick, k_cover_merge) and the synthetic cases that reach
 the kernels' data-independent regimes -- TEST INFRASTRUCTURE ONLY.
 
 Nothing here calls the library.  cover() is vectorised numpy over (P, words) uint64 masks, so that

@@ -1,4 +1,4 @@
-"""GPU: the greedy set cover (csrc/dmf_trace.hip: k_cover_gain, k_cover_pick,
+"""GPU: the greedy set cover (csrc/dmf_cover.hip: k_cover_gain, k_cover_pick,
 k_cover_merge) on the synthetic masks of tests/cover_ref.py, through
 dmf_greedy_set_cover_masks_device.  The rendered scenes of the other GPU tests never tie, never pass
 30 sets and a few hundred words, and never stop at min_gain itself; the named cases do (each one's

@@ -709,6 +709,15 @@ def test_fuse_variant_controls(dmf):
     assert _lib.kernel_name(a) == "dmf::k_bk_fuse<16, 8, 8>" and _lib.kernel_name(b).startswith("dmf::k_bk_fuse_s<")
     assert L.dmf_fuse_set_variant(a._h, 53) == _lib.DMF_ERR_INVALID
     assert L.dmf_volume_set_knob(a._h, 99, 1) == _lib.DMF_ERR_INVALID
+    # a kernel choice outside the kernels there are is rejected and leaves the knob as it was
+    for name, last in (("reverse_kernel", 5), ("fwd_kernel", 2)):
+        k = _lib.KNOBS[name]
+        assert L.dmf_volume_set_knob(a._h, k, last) == _lib.DMF_OK
+        for bad in (-1, last + 1):
+            assert L.dmf_volume_set_knob(a._h, k, bad) == _lib.DMF_ERR_INVALID
+        _lib.check(L.dmf_volume_get_knob(a._h, k, C.addressof(kb)))
+        assert kb.value == last
+        assert L.dmf_volume_set_knob(a._h, k, 0) == _lib.DMF_OK
 
 
 def test_fuse_brick_vs_lds_box_full_size(dmf):

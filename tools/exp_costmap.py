@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Timing of the collision cost map (round 5: A/B of an experiment build's DMF_KNOB_COST_SKIP, 0 =
-empty-space jumps between 64-depth groups, -1 = off; argv[1] = comma-separated list, alternated;
-the knob is gone from the product) on bench.py's secondary workload: 1024 centres on a 0.45 m
-sphere (scene.sphere_centres) in the 512^3 volume integrated from 16 back-projected 640x480
-frames.  Prints ms per launch for each, whether the maps are identical, and the map's digest
-against tests/golden/march_digests.json (costmap_digest)."""
+"""Timing of the collision cost map (k_cost_map; argv[1] = repetitions, default 4) on bench.py's
+secondary workload: 1024 centres on a 0.45 m sphere (scene.sphere_centres) in the 512^3 volume
+integrated from 16 back-projected 640x480 frames.  Prints ms per launch of each repetition,
+whether the maps are identical, and the map's digest against tests/golden/march_digests.json
+(costmap_digest).  (Round 5's A/B of empty-space jumps between 64-depth groups ran on an
+experiment build)"""
 import ctypes as C
 import json
 import os
@@ -45,15 +45,15 @@ Vc = 1024
 cp = scene.sphere_centres(Vc)
 d_cp = torch.from_numpy(cp).to(dev)
 cmap = torch.empty((Vc, Vc), dtype=torch.int32, device=dev)
-out = {"centres": Vc}
-res = {}
-KS = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [0, -1, 0, -1]
-for k in KS:
-    if "cost_skip" in _lib.KNOBS:
-        _lib.set_knob(vol, "cost_skip", k)
+out = {"centres": Vc, "ms": []}
+res = []
 
-    def run():
-        _lib.check(L.dmf_collision_cost_map_device(vol._h, d_cp.data_ptr(), Vc, cmap.data_ptr()))
+
+def run():
+    _lib.check(L.dmf_collision_cost_map_device(vol._h, d_cp.data_ptr(), Vc, cmap.data_ptr()))
+
+
+for _ in range(int(sys.argv[1]) if len(sys.argv) > 1 else 4):
     run()
     torch.cuda.synchronize(dev)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -62,13 +62,12 @@ for k in KS:
         run()
     e1.record(s)
     torch.cuda.synchronize(dev)
-    out.setdefault(f"ms_skip{k}", []).append(round(e0.elapsed_time(e1) / 5, 4))
-    res[k] = cmap.cpu().numpy().copy()
-k0 = KS[0]
-out["maps_equal"] = bool(all(np.array_equal(res[k0], r) for r in res.values()))
-out["collided"] = int((res[k0] == 0x7FFFFFFF).sum())
+    out["ms"].append(round(e0.elapsed_time(e1) / 5, 4))
+    res.append(cmap.cpu().numpy().copy())
+out["maps_equal"] = bool(all(np.array_equal(res[0], r) for r in res))
+out["collided"] = int((res[0] == 0x7FFFFFFF).sum())
 import hashlib
-out["digest"] = {k: hashlib.sha256(np.ascontiguousarray(r).tobytes()).hexdigest()[:16] for k, r in res.items()}
+out["digest"] = hashlib.sha256(np.ascontiguousarray(res[0]).tobytes()).hexdigest()[:16]
 try:
     out["digest_expected"] = json.load(open(os.path.join(ROOT, "tests", "golden", "march_digests.json")))["config4_shard_N1"]["costmap_digest"]
 except (OSError, KeyError) as e:
