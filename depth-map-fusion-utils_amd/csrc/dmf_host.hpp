@@ -80,6 +80,10 @@ enum ScratchSlot {
   // the travel field (dmf_travel.hip): the traversable mask and its tile level, the two active-tile
   // lists with their "queued" bits, the counters and list lengths, and the host forms' field
   kScTrFine, kScTrCoarse, kScTrQueue, kScTrCtl, kScTrHops,
+  // cloud nearest neighbour (dmf_cloud.hip): the control block, the cells' counts and offsets, the
+  // cell-sorted records, the sorted variant's keys, and the host form's staging of both clouds,
+  // both per-point outputs and the summaries
+  kScClCtl, kScClCells, kScClRec, kScClKeys, kScClQuery, kScClRef, kScClDist, kScClIndex, kScClSums,
   // brick-owned fusion (dmf_fuse.hip): one block, buffer b of staging slot s at bk_key(b, s)
   kScBkFirst, kScBkEnd = kScBkFirst + 2 * kBkBufCount
 };

@@ -19,6 +19,7 @@ is no CPU fallback.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -37,6 +38,11 @@ NO_DIST = np.uint32(0xFFFFFFFF)
 # VoxelVolume.travel_field: a cell that is not traversable or not reachable (DMF_NO_PATH, include/dmf.h;
 # a grid of at most 2^31 cells has no hop count of all ones)
 NO_PATH = np.uint32(0xFFFFFFFF)
+# VoxelVolume.cloud_nearest: the index of a query that has no neighbour (DMF_NO_POINT, include/dmf.h)
+NO_POINT = -1
+
+CloudError = collections.namedtuple("CloudError", "n_valid max_error avg_error over dist2")
+SurfaceError = collections.namedtuple("SurfaceError", "n_surface n_valid max_error avg_error over dist2")
 
 
 def degree(radian):
@@ -420,6 +426,116 @@ class VoxelVolume:
             for p in bufs:
                 self._L.dmf_device_free(self._h, p)
         return out
+
+    # -- exact nearest neighbour between clouds and the cloud error, on the GPU
+    @staticmethod
+    def _cloud(a, name):
+        p = np.asarray(a)
+        if p.dtype != np.float32 and not (p.dtype.kind in "fiu" and np.can_cast(p.dtype, np.float32, "safe")):
+            raise ValueError(f"{name} must be float32 (or a type that float32 holds exactly), got {p.dtype}")
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError(f"{name} must have shape (n, 3), got {p.shape}")
+        return np.ascontiguousarray(p, np.float32)
+
+    @staticmethod
+    def _thresholds(thresholds):
+        t = np.asarray(list(thresholds), np.float64).reshape(-1)
+        if t.size > 8:
+            raise ValueError(f"at most 8 thresholds, got {t.size}")
+        if not (t >= 0).all():
+            raise ValueError(f"thresholds must be non-negative, got {t.tolist()}")
+        return t
+
+    def cloud_nearest(self, query, ref):
+        """For every point of `query` (float32 (n, 3)) its exact nearest neighbour in `ref` (float32
+        (m, 3)) -> (dist2 float32 (n,), index int32 (n,)): the least d2 = (dx*dx + dy*dy) + dz*dz in
+        float32 over the reference points with finite coordinates and the lowest index that attains
+        it; +inf and NO_POINT for a query with a non-finite coordinate, and for every query when the
+        reference has no valid point.  What ErrorCalc.cpp asks of PCL's k-d tree, for all points in
+        one call.  The volume only lends its device, stream and scratch: it need not be constructed."""
+        q, r = self._cloud(query, "query"), self._cloud(ref, "ref")
+        n = q.shape[0]
+        d2, idx = np.empty(n, np.float32), np.empty(n, np.int32)
+        if n:
+            check(self._L.dmf_cloud_nearest(self._h, ptr(q), n, ptr(r) if r.shape[0] else None, r.shape[0], ptr(d2),
+                                            ptr(idx), None, 0, None, None))
+        return d2, idx
+
+    def cloud_error(self, query, ref, thresholds=(0.003, 0.005)):
+        """The error of the cloud `query` against the model cloud `ref` as tests/ErrorCalc.cpp:74-97
+        reports it -> CloudError(n_valid, max_error, avg_error, over, dist2): the queries that have a
+        neighbour, the largest and the mean of their distances sqrtf(dist2), how many of them lie
+        beyond each threshold (metres; the reference marks 3 mm and 5 mm), and dist2 (float32 (n,))
+        of cloud_nearest.  avg_error is formed as the reference's loop forms it: sqrtf in float,
+        accumulated in a double in index order, divided by n_valid (nan when that is 0); max_error is
+        -1.0 when n_valid is 0, the reference's initial value."""
+        q, r = self._cloud(query, "query"), self._cloud(ref, "ref")
+        t = self._thresholds(thresholds)
+        n = q.shape[0]
+        d2 = np.empty(n, np.float32)
+        cnt, sums = np.zeros(2 + t.size, np.uint64), np.zeros(2, np.float64)
+        check(self._L.dmf_cloud_nearest(self._h, ptr(q) if n else None, n, ptr(r) if r.shape[0] else None, r.shape[0],
+                                        ptr(d2) if n else None, None, ptr(t) if t.size else None, t.size, ptr(cnt),
+                                        ptr(sums)))
+        # a query has a neighbour iff it is valid and the reference has a valid point
+        has = np.isfinite(q).all(axis=1) if int(cnt[1]) else np.zeros(n, bool)
+        nv = int(cnt[0])
+        dist = np.sqrt(d2[has]).astype(np.float64)
+        avg = float(np.cumsum(dist)[-1] / nv) if nv else float("nan")
+        return CloudError(nv, float(sums[0]), avg, tuple(int(c) for c in cnt[2:]), d2)
+
+    def surface_error(self, logodds, ref, occ_threshold=1, free_threshold=-1, thresholds=(0.003, 0.005),
+                      per_point=False):
+        """The error of the fused grid's surface (extract_surface's voxel centres, in its order)
+        against the model cloud `ref`, without the surface leaving the device ->
+        SurfaceError(n_surface, n_valid, max_error, avg_error, over, dist2): only the surface count
+        and the summaries come back, and dist2 (float32 (n_surface,)) with per_point=True (else
+        None).  avg_error is the device's sum of the distances over n_valid (its order of additions
+        is unspecified; nan when n_valid is 0)."""
+        lo = self._logodds(logodds)
+        r = self._cloud(ref, "ref")
+        t = self._thresholds(thresholds)
+        args = (int(occ_threshold), int(free_threshold))
+        bufs = []
+
+        def alloc(nbytes):
+            p = C.c_void_p()
+            check(self._L.dmf_device_malloc(self._h, C.addressof(p), max(int(nbytes), 8)))
+            bufs.append(p.value)
+            return p.value
+
+        try:
+            d_grid, d_count, d_ref = alloc(lo.nbytes), alloc(16), alloc(r.nbytes)
+            check(self._L.dmf_memcpy_h2d(self._h, d_grid, ptr(lo), lo.nbytes))
+            if r.nbytes:
+                check(self._L.dmf_memcpy_h2d(self._h, d_ref, ptr(r), r.nbytes))
+            # the count first (capacity 0: nothing is written), then the centres into a buffer of that size
+            count = np.zeros(2, np.uint64)
+            check(self._L.dmf_grid_surface_device(self._h, d_grid, *args, None, alloc(8), None, 0, d_count))
+            check(self._L.dmf_memcpy_d2h(self._h, ptr(count), d_count, 16))
+            n = int(count[0])
+            d_xyz = alloc(12 * n)
+            if n:
+                check(self._L.dmf_grid_surface_device(self._h, d_grid, *args, None, d_xyz, None, n, d_count))
+            d_d2 = alloc(4 * n) if per_point and n else None
+            d_cnt, d_sums = alloc(8 * (2 + t.size)), alloc(16)
+            check(self._L.dmf_cloud_nearest_device(self._h, d_xyz if n else None, n, d_ref if r.shape[0] else None,
+                                                   r.shape[0], d_d2, None, ptr(t) if t.size else None, t.size, d_cnt,
+                                                   d_sums))
+            cnt, sums = np.zeros(2 + t.size, np.uint64), np.zeros(2, np.float64)
+            check(self._L.dmf_memcpy_d2h(self._h, ptr(cnt), d_cnt, cnt.nbytes))
+            check(self._L.dmf_memcpy_d2h(self._h, ptr(sums), d_sums, sums.nbytes))
+            d2 = None
+            if per_point:
+                d2 = np.empty(n, np.float32)
+                if n:
+                    check(self._L.dmf_memcpy_d2h(self._h, ptr(d2), d_d2, d2.nbytes))
+        finally:
+            for p in bufs:
+                self._L.dmf_device_free(self._h, p)
+        nv = int(cnt[0])
+        return SurfaceError(n, nv, float(sums[0]), float(sums[1]) / nv if nv else float("nan"),
+                            tuple(int(c) for c in cnt[2:]), d2)
 
     @property
     def occupied_cells_(self):

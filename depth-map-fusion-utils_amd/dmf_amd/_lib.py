@@ -149,6 +149,10 @@ SIGNATURES = {
     "dmf_grid_path": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
     "dmf_grid_path_device": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
     "dmf_grid_travel_stats": (C.c_int, [_vp, _p]),
+    "dmf_cloud_nearest": (C.c_int, [_vp, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _p]),
+    "dmf_cloud_nearest_device": (C.c_int, [_vp, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _p]),
+    "dmf_cloud_nearest_stats": (C.c_int, [_vp, _p]),
+    "dmf_cloud_nearest_set_variant": (C.c_int, [_vp, _i32, _i32]),
     "dmf_fuse_counter_cells": (C.c_int, [_vp, _p]),
     "dmf_fuse_counters_to_linear_device": (C.c_int, [_vp, _p, _p]),
     "dmf_fuse_reserve": (C.c_int, [_vp, _p, _i32, C.c_uint64]),
@@ -263,6 +267,12 @@ def set_variant(vol, variant):
 def kernel_name(vol):
     """dmf_fuse_kernel_name: the fusion kernel of the volume's latest call."""
     return load().dmf_fuse_kernel_name(getattr(vol, "_h", vol)).decode()
+
+
+def cloud_variant(vol, occ=0, order=0):
+    """dmf_cloud_nearest_set_variant: the cloud nearest neighbour's target points per cell and query
+    order (1 given, 2 sorted by home cell); 0 = the default."""
+    check(load().dmf_cloud_nearest_set_variant(getattr(vol, "_h", vol), int(occ), int(order)))
 
 
 def set_knob(vol, name, value):

@@ -546,6 +546,48 @@ int dmf_grid_path(dmf_volume* v, const uint32_t* hops, const int32_t* target3, i
 int dmf_grid_path_device(dmf_volume* v, const uint32_t* d_hops, const int32_t* d_target3, int32_t* d_cells,
                          int64_t cap, uint64_t* d_n);
 
+/* Exact nearest neighbour of every point of one cloud in another, and the cloud error built on it
+ * (DESIGN.md §4.7): what the reference's tests/ErrorCalc.cpp:71-97 asks of PCL's k-d tree
+ * (nearestKSearch(pt, 1, ...)) one point at a time -- how far a reconstruction lies from a model.
+ * query[n][3] and ref[m][3] are packed float32 points in the world frame; no alignment beyond 4
+ * bytes is owed.  For a query q and a reference point r, all in float32 with no contraction,
+ *   d2(q, r) = (dx*dx + dy*dy) + dz*dz,  dx = q.x - r.x and likewise dy, dz
+ * (the accumulation order of the L2_Simple<float> functor of PCL's KdTreeFLANN).  A point is valid
+ * iff its three coordinates are finite.  Each output may be NULL (not all four):
+ *   dist2[i]  (float)  the minimum of d2(query[i], ref[j]) over the valid j;
+ *   index[i]  (int32)  the LOWEST j that attains it;
+ *             an invalid query gives dist2 = +inf and index = DMF_NO_POINT, and so does every query
+ *             when no reference point is valid (m = 0 included);
+ *   counts[2 + T] (uint64), written, not accumulated: {the valid queries that have a neighbour, the
+ *             valid reference points, then for each of the T <= 8 thresholds t_k (doubles, read
+ *             from a HOST pointer in both forms) how many of those queries have
+ *             (double)sqrtf(dist2) > t_k} -- the reference's compare (ErrorCalc.cpp:82-91, 3 mm and
+ *             5 mm; its else-if branch for 5 mm can never be taken, hence counts, not a colour);
+ *   sums[2]   (double) {the largest (double)sqrtf(dist2) over the queries counted in counts[0],
+ *             exact, and -1.0 when there are none (the reference's initial value); the sum of those
+ *             distances, in an unspecified order (ErrorCalc.cpp's avg_error times its count, up to
+ *             the rounding of the additions)}.
+ * There is no search radius and no approximation: the result equals a brute-force scan bit for bit
+ * on any input.  Limits: m <= 2^31 - 1; n is an int64.  A strongly clustered reference (one
+ * outlier that stretches the box until the rest falls into one cell of the index) stays exact but
+ * degenerates towards brute force over that cell.
+ * The calls need only a CREATED volume, for its device, stream and scratch: the volume's geometry
+ * and point-cloud occupancy are neither read nor changed, and an UNCONSTRUCTED volume is fine here
+ * (every other grid call returns DMF_ERR_STATE for one).
+ * Device form: device pointers (thresholds: host), only enqueues on the volume's stream, allocates
+ * only when its scratch (16 B per reference point, at most 32 MiB of cells) must grow and reuses it
+ * otherwise.  Host form: host pointers, synchronises.
+ * A null v, a null query with n > 0, a null ref with m > 0, all four outputs null, a negative n or
+ * m, T outside 0..8 and T > 0 with null thresholds are DMF_ERR_INVALID, all checked before anything
+ * is touched; m >= 2^31 is DMF_ERR_RANGE.  n = 0 is DMF_OK and writes only the summaries
+ * (counts[0] = 0, sums = {-1, 0}). */
+#define DMF_NO_POINT (-1)
+int dmf_cloud_nearest(dmf_volume* v, const float* query, int64_t n, const float* ref, int64_t m, float* dist2,
+                      int32_t* index, const double* thresholds, int32_t T, uint64_t* counts, double* sums);
+int dmf_cloud_nearest_device(dmf_volume* v, const float* d_query, int64_t n, const float* d_ref, int64_t m,
+                             float* d_dist2, int32_t* d_index, const double* thresholds, int32_t T,
+                             uint64_t* d_counts, double* d_sums);
+
 /* ---- multi-GPU merge over RCCL ------------------------
  * Poses shard across ranks, each rank fuses into its own replica of the counters, and
  * the replicas merge with integer collectives (bit-identical to one rank fusing all

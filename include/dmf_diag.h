@@ -79,6 +79,18 @@ int dmf_volume_get_knob(const dmf_volume* v, int32_t knob, int64_t* value);
  * otherwise. */
 int dmf_grid_travel_stats(const dmf_volume* v, uint64_t* stats4);
 
+/* The volume's latest dmf_cloud_nearest* call (waits for it): stats4 = {reference points examined,
+ * shells of cells scanned, the cells of the index, the valid reference points}; the first two are
+ * summed over the queries, counted only by a library built with -DDMF_EXP_STATS and 0 otherwise.
+ * All 0 before any such call. */
+int dmf_cloud_nearest_stats(const dmf_volume* v, uint64_t* stats4);
+/* The A/B controls of dmf_cloud_nearest* (DESIGN.md §5.17), per volume; every value gives identical
+ * results.  occ: the target mean of reference points per cell of the index's box, 1..1024 (0 = the
+ * default, 4).  order: 1 = the queries in the order given, 2 = the queries sorted by home cell first,
+ * with an index indirection on output (query counts below 2^32 only; 0 = the default, 2).  Any other
+ * value is DMF_ERR_INVALID. */
+int dmf_cloud_nearest_set_variant(dmf_volume* v, int32_t occ, int32_t order);
+
 /* OccupancyGrid: downloadReorganizedCloud (modes 2 / 3 of dmf_ogrid_download) iterates fixed-point
  * rounds and, when they do not settle within the cap, runs the sequential loop on one lane; both
  * give the same cloud.  rounds: the rounds the grid's latest mode-2/3 download ran until its fixed
