@@ -47,7 +47,8 @@ inline std::vector<std::vector<int>> collisionCostMap(VoxelVolume& volume, const
 // The fused grid's counterpart of collisionCostMap, with detours (dmf_grid_travel_device, DESIGN.md
 // §4.6; not in the reference): map[i][j] = the least number of face-to-face steps from cells[i] to
 // cells[j] through cells with dist2 >= radius2, INT_MAX where there is no path.  One travel field
-// per row into one device buffer; only the row's V entries come back.
+// per row into one device buffer and a gather of the row's V entries (dmf_grid_travel_cost_map);
+// the map comes back in one copy.
 inline std::vector<std::vector<int>> travelCostMap(VoxelVolume& volume, const std::vector<uint32_t>& dist2,
                                                    uint32_t radius2, const std::vector<std::array<int32_t, 3>>& cells) {
   const int32_t V = (int32_t)cells.size();
@@ -55,29 +56,10 @@ inline std::vector<std::vector<int>> travelCostMap(VoxelVolume& volume, const st
   if (dist2.size() != (size_t)nx * ny * nz) throw std::invalid_argument("travelCostMap: field size");
   std::vector<std::vector<int>> map(V, std::vector<int>(V, INT_MAX));
   if (V == 0) return map;
-  dmf_volume* v = volume.handle();
-  const size_t bytes = sizeof(uint32_t) * dist2.size();
-  void *d_d2 = nullptr, *d_hops = nullptr, *d_seeds = nullptr;
-  int st = dmf_device_malloc(v, &d_d2, bytes);
-  if (st == DMF_OK) st = dmf_device_malloc(v, &d_hops, bytes);
-  if (st == DMF_OK) st = dmf_device_malloc(v, &d_seeds, sizeof(int32_t) * 3 * (size_t)V);
-  if (st == DMF_OK) st = dmf_memcpy_h2d(v, d_d2, dist2.data(), bytes);
-  if (st == DMF_OK) st = dmf_memcpy_h2d(v, d_seeds, cells[0].data(), sizeof(int32_t) * 3 * (size_t)V);
-  for (int32_t i = 0; i < V && st == DMF_OK; ++i) {
-    st = dmf_grid_travel_device(v, (const uint32_t*)d_d2, radius2, (const int32_t*)d_seeds + 3 * (size_t)i, 1,
-                                (uint32_t*)d_hops, nullptr);
-    for (int32_t j = 0; j < V && st == DMF_OK; ++j) {
-      const std::array<int32_t, 3>& c = cells[j];
-      if (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] >= nx || c[1] >= ny || c[2] >= nz) continue;
-      uint32_t h = DMF_NO_PATH;
-      st = dmf_memcpy_d2h(v, &h, (const uint32_t*)d_hops + ((size_t)c[0] * ny + c[1]) * nz + c[2], sizeof(h));
-      if (st == DMF_OK && h != DMF_NO_PATH) map[i][j] = (int)h;
-    }
-  }
-  if (d_seeds) dmf_device_free(v, d_seeds);
-  if (d_hops) dmf_device_free(v, d_hops);
-  if (d_d2) dmf_device_free(v, d_d2);
-  dmf_check(st);
+  std::vector<int32_t> flat((size_t)V * V);
+  dmf_check(dmf_grid_travel_cost_map(volume.handle(), dist2.data(), radius2, cells[0].data(), V, flat.data()));
+  for (int32_t i = 0; i < V; ++i)
+    for (int32_t j = 0; j < V; ++j) map[i][j] = flat[(size_t)i * V + j];
   return map;
 }
 

@@ -84,6 +84,9 @@ enum ScratchSlot {
   // cell-sorted records, the sorted variant's keys, and the host form's staging of both clouds,
   // both per-point outputs and the summaries
   kScClCtl, kScClCells, kScClRec, kScClKeys, kScClQuery, kScClRef, kScClDist, kScClIndex, kScClSums,
+  // the tour (dmf_tour.hip): the control block, the four prefix arrays with the permutation check's
+  // bits, and the host forms' map, path and info
+  kScToCtl, kScToPre, kScToMap, kScToPath, kScToInfo,
   // brick-owned fusion (dmf_fuse.hip): one block, buffer b of staging slot s at bk_key(b, s)
   kScBkFirst, kScBkEnd = kScBkFirst + 2 * kBkBufCount
 };

@@ -297,6 +297,8 @@ struct dmf_volume {
   int64_t knob[DMF_KNOB_COUNT] = {};
   // the latest travel-field call (dmf_grid_travel_stats): rounds, launches, tile activations, cell updates
   uint64_t travel_stats[4] = {0, 0, 0, 0};
+  // the latest 2-opt solve (dmf_tour_stats): rounds launched, batches, improvements, candidates ahead of the applied ones
+  uint64_t tour_stats[4] = {0, 0, 0, 0};
   // cloud nearest neighbour (dmf_cloud_nearest_set_variant): target points per cell and query order, 0 = the defaults
   int cloud_occ = 0, cloud_order = 0;
   // scratch arena

@@ -21,12 +21,14 @@
 //                upper bound either way and is activated for the next round.  No workgroup waits
 //                for another;
 //  k_tr_finish — one streaming pass over hops: the reached cells and the largest finite value;
+//  k_tr_gather — one row of the travel cost map: the hop counts at V cells, INT_MAX for no path;
 //  k_tr_path   — one lane walks target -> seed: from value k to the first face neighbour, in the
 //                order -x +x -y +y -z +z, that holds k - 1.
 // The host reads the next list's length after a batch of kTrBatch rounds and stops at an empty
 // list; T + 2 rounds (T = the traversable cells) bound the loop: a cell whose shortest path crosses
 // k tile faces is final after round k, and k < T.
 #include <algorithm>
+#include <climits>
 
 #include "dmf_host.hpp"
 
@@ -305,6 +307,17 @@ __global__ __launch_bounds__(64) void k_tr_path(Geom g, const uint32_t* __restri
   *n = len;
 }
 
+// One row of the travel cost map: row[j] = hops at cells[j], INT_MAX for DMF_NO_PATH or a cell outside the grid.
+__global__ __launch_bounds__(256) void k_tr_gather(Geom g, const uint32_t* __restrict__ hops,
+                                                   const int32_t* __restrict__ cells, int V, int32_t* __restrict__ row) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= V) return;
+  const int x = cells[3 * j], y = cells[3 * j + 1], z = cells[3 * j + 2];
+  uint32_t h = kTrNone;
+  if (x >= 0 && y >= 0 && z >= 0 && x < g.n[0] && y < g.n[1] && z < g.n[2]) h = hops[((int64_t)x * g.n[1] + y) * g.n[2] + z];
+  row[j] = h == kTrNone ? INT_MAX : (int32_t)h;  // (a hop count is below 2^31: require_travel_grid)
+}
+
 // The plain arguments first (no access to the volume: they are rejected without a device).
 static int check_travel_args(const dmf_volume* v, const void* dist2, const void* seeds, int64_t n_seeds,
                              const void* hops) {
@@ -403,6 +416,31 @@ static int travel_device(dmf_volume* v, const uint32_t* d_dist2, uint32_t radius
   return DMF_OK;
 }
 
+constexpr int kTrMaxCostCells = 46340;  // V * V < 2^31, the limit of dmf_tour*
+static int check_cost_map_args(const dmf_volume* v, const void* dist2, const void* cells, int32_t V, const void* map) {
+  if (!v || !dist2) return fail(DMF_ERR_INVALID, "null argument");
+  if (V < 0) return fail(DMF_ERR_INVALID, "negative V %d", V);
+  if (V > kTrMaxCostCells) return fail(DMF_ERR_RANGE, "the travel cost map is limited to %d cells, got %d", kTrMaxCostCells, V);
+  if (V > 0 && (!cells || !map)) return fail(DMF_ERR_INVALID, "null argument with V = %d", V);
+  return DMF_OK;
+}
+
+// One travel field per row into the scratch hop buffer, then the row's gather.
+static int cost_map_device(dmf_volume* v, const uint32_t* d_dist2, uint32_t radius2, const int32_t* d_cells, int V,
+                           int32_t* d_map) {
+  if (V == 0) return DMF_OK;
+  void* dh;
+  DMF_TRY(scratch(v, kScTrHops, sizeof(uint32_t) * v->ncell, &dh));
+  for (int i = 0; i < V; ++i) {
+    DMF_TRY(travel_device(v, d_dist2, radius2, d_cells + 3 * (size_t)i, 1, (uint32_t*)dh, nullptr, nullptr));
+    hipLaunchKernelGGL(k_tr_gather, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, v->stream, v->geom(),
+                       (const uint32_t*)dh, d_cells, V, d_map + (size_t)i * V);
+    DMF_LAUNCH_CHECK();
+  }
+  DMF_HIP(hipStreamSynchronize(v->stream));
+  return DMF_OK;
+}
+
 static int path_device(dmf_volume* v, const uint32_t* d_hops, const int32_t* d_target, int32_t* d_cells, int64_t cap,
                        uint64_t* d_n) {
   hipLaunchKernelGGL(k_tr_path, dim3(1), dim3(64), 0, v->stream, v->geom(), d_hops, d_target, d_cells, cap,
@@ -441,6 +479,35 @@ int dmf_grid_travel(dmf_volume* v, const uint32_t* dist2, uint32_t radius2, cons
   }
   DMF_TRY(travel_device(v, (const uint32_t*)dd, radius2, (const int32_t*)ds, n_seeds, (uint32_t*)dh, nullptr, info3));
   DMF_HIP(hipMemcpyAsync(hops, dh, sizeof(uint32_t) * v->ncell, hipMemcpyDeviceToHost, v->stream));
+  DMF_HIP(hipStreamSynchronize(v->stream));
+  return DMF_OK;
+  DMF_API_END
+}
+
+int dmf_grid_travel_cost_map_device(dmf_volume* v, const uint32_t* d_dist2, uint32_t radius2, const int32_t* d_cells,
+                                    int32_t V, int32_t* d_map) {
+  DMF_API_BEGIN
+  DMF_TRY(check_cost_map_args(v, d_dist2, d_cells, V, d_map));
+  DMF_TRY(require_travel_grid(v));
+  return cost_map_device(v, d_dist2, radius2, d_cells, V, d_map);
+  DMF_API_END
+}
+
+int dmf_grid_travel_cost_map(dmf_volume* v, const uint32_t* dist2, uint32_t radius2, const int32_t* cells, int32_t V,
+                             int32_t* map) {
+  DMF_API_BEGIN
+  DMF_TRY(check_cost_map_args(v, dist2, cells, V, map));
+  DMF_TRY(require_travel_grid(v));
+  if (V == 0) return DMF_OK;
+  void *dd, *dc, *dm;
+  const size_t mapb = sizeof(int32_t) * (size_t)V * (size_t)V;
+  DMF_TRY(scratch(v, kScDfDist, sizeof(uint32_t) * v->ncell, &dd));
+  DMF_TRY(scratch(v, kScHost1, sizeof(int32_t) * 3 * (size_t)V, &dc));
+  DMF_TRY(scratch(v, kScOut0, mapb, &dm));
+  DMF_HIP(hipMemcpyAsync(dd, dist2, sizeof(uint32_t) * v->ncell, hipMemcpyHostToDevice, v->stream));
+  DMF_HIP(hipMemcpyAsync(dc, cells, sizeof(int32_t) * 3 * (size_t)V, hipMemcpyHostToDevice, v->stream));
+  DMF_TRY(cost_map_device(v, (const uint32_t*)dd, radius2, (const int32_t*)dc, V, (int32_t*)dm));
+  DMF_HIP(hipMemcpyAsync(map, dm, mapb, hipMemcpyDeviceToHost, v->stream));
   DMF_HIP(hipStreamSynchronize(v->stream));
   return DMF_OK;
   DMF_API_END

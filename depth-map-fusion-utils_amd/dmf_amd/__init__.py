@@ -390,41 +390,16 @@ class VoxelVolume:
         """The V x V travel cost map of the cells `cells` (integers, (V, 3)) -> int32 (V, V):
         entry [i][j] = the hop count from cells[i] to cells[j] through cells with dist2 >= radius2,
         INT_MAX where there is no path -- the fused grid's counterpart of collisionCostMap, with
-        detours.  One travel field per row, made on the device into one reused buffer; only the
-        row's V entries come back."""
+        detours.  One travel field per row, made on the device into one reused buffer, and a gather
+        of the row's V entries; the map comes back in one copy."""
         d2 = self._field(dist2, "dist2")
         c = self._cells(cells, "cells")
         if not 0 <= int(radius2) <= 0xFFFFFFFF:
             raise ValueError(f"radius2 must fit uint32, got {radius2}")
         V = c.shape[0]
-        nx, ny, nz = self.dims
         out = np.full((V, V), 2147483647, np.int32)
-        if V == 0:
-            return out
-        inside = ((c >= 0) & (c < np.array([nx, ny, nz]))).all(axis=1)
-        flat = (c[:, 0].astype(np.int64) * ny + c[:, 1]) * nz + c[:, 2]
-        bufs = []
-
-        def alloc(nbytes):
-            p = C.c_void_p()
-            check(self._L.dmf_device_malloc(self._h, C.addressof(p), max(int(nbytes), 8)))
-            bufs.append(p.value)
-            return p.value
-
-        try:
-            d_d2, d_hops, d_seeds = alloc(d2.nbytes), alloc(d2.nbytes), alloc(c.nbytes)
-            check(self._L.dmf_memcpy_h2d(self._h, d_d2, ptr(d2), d2.nbytes))
-            check(self._L.dmf_memcpy_h2d(self._h, d_seeds, ptr(c), c.nbytes))
-            one = np.zeros(1, np.uint32)
-            for i in range(V):
-                check(self._L.dmf_grid_travel_device(self._h, d_d2, int(radius2), d_seeds + 12 * i, 1, d_hops, None))
-                for j in np.flatnonzero(inside):
-                    check(self._L.dmf_memcpy_d2h(self._h, ptr(one), d_hops + 4 * int(flat[j]), 4))
-                    if one[0] != NO_PATH:
-                        out[i, j] = int(one[0])
-        finally:
-            for p in bufs:
-                self._L.dmf_device_free(self._h, p)
+        if V:
+            check(self._L.dmf_grid_travel_cost_map(self._h, ptr(d2), int(radius2), ptr(c), V, ptr(out)))
         return out
 
     # -- exact nearest neighbour between clouds and the cloud error (DESIGN.md §4.7), on the GPU
@@ -882,6 +857,65 @@ def collision_cost_map(volume, poses):
     out = np.zeros((V, V), np.int32)
     check(volume._L.dmf_collision_cost_map(volume._h, ptr(poses), V, ptr(out)))
     return out
+
+
+def _tour_map(cost_map):
+    m = np.asarray(cost_map)
+    if m.dtype != np.int32 or m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError(f"cost_map must be int32 of shape (V, V), got {m.dtype} {m.shape}")
+    return np.ascontiguousarray(m)
+
+
+def _tour_result(path, cnt, info):
+    # (the edge sum is an int64 in its uint64 word: entries may be negative)
+    return (path, tuple(int(c) for c in cnt[:3]) + (int(cnt.view(np.int64)[3]), int(cnt[4]))) if info else path
+
+
+def tour_nearest_neighbour(volume, cost_map, info=False):
+    """TSP::NearestNeighborSearch (TSPSolver.hpp:76-98) over `cost_map` (int32 (V, V), [a][b] = the
+    cost from a to b, INT_MAX = no edge) -> the int32 path (V,), from node 0; on the GPU
+    (DESIGN.md §4.8).  Where every unvisited entry of a row is INT_MAX the lowest unvisited index
+    is taken (the reference aborts).  info=True also returns (forced picks, 0, 0, the sum of the
+    path's edges below INT_MAX, its INT_MAX edges).  `volume` supplies the device and stream."""
+    m = _tour_map(cost_map)
+    V = m.shape[0]
+    path, cnt = np.zeros(V, np.int32), np.zeros(5, np.uint64)
+    check(volume._L.dmf_tour_nearest_neighbour(volume._h, ptr(m) if V else None, V, ptr(path) if V else None, ptr(cnt)))
+    return _tour_result(path, cnt, info)
+
+
+def tour_two_opt(volume, cost_map, path, max_rounds=0, info=False):
+    """TSP::TwoOptSearch (TSPSolver.hpp:136-156) from `path` (a permutation of 0..V-1; position 0
+    stays) -> the improved int32 path: the first candidate (i, k) in lexicographic order whose
+    reversal of positions i..k makes the path strictly shorter is applied and the scan restarts,
+    until none is left or `max_rounds` > 0 reversals are applied.  info=True also returns (0,
+    reversals, converged 0/1, the sum of the edges below INT_MAX, the INT_MAX edges)."""
+    m = _tour_map(cost_map)
+    V = m.shape[0]
+    p = np.asarray(path)
+    if p.dtype.kind not in "iu" or p.shape != (V,):
+        raise ValueError(f"path must be integer indices of shape ({V},), got {p.dtype} {p.shape}")
+    if V and (int(p.min()) < -2 ** 31 or int(p.max()) >= 2 ** 31):
+        raise ValueError("path holds an index that int32 does not hold")   # (it would wrap in the cast below)
+    if int(max_rounds) < 0:
+        raise ValueError(f"max_rounds must be >= 0, got {max_rounds}")
+    out, cnt = np.array(p, np.int32), np.zeros(5, np.uint64)
+    check(volume._L.dmf_tour_two_opt(volume._h, ptr(m) if V else None, V, ptr(out) if V else None, int(max_rounds),
+                                     ptr(cnt)))
+    return _tour_result(out, cnt, info)
+
+
+def tour(volume, cost_map, max_rounds=0, info=False):
+    """tour_nearest_neighbour, then tour_two_opt from its path: what every planner of the reference
+    runs over its cost map (run_tsp).  info=True also returns (forced picks, reversals, converged
+    0/1, the sum of the edges below INT_MAX, the INT_MAX edges)."""
+    m = _tour_map(cost_map)
+    V = m.shape[0]
+    if int(max_rounds) < 0:
+        raise ValueError(f"max_rounds must be >= 0, got {max_rounds}")
+    path, cnt = np.zeros(V, np.int32), np.zeros(5, np.uint64)
+    check(volume._L.dmf_tour(volume._h, ptr(m) if V else None, V, ptr(path) if V else None, int(max_rounds), ptr(cnt)))
+    return _tour_result(path, cnt, info)
 
 
 class OccupancyGrid:

@@ -149,6 +149,15 @@ SIGNATURES = {
     "dmf_grid_path": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
     "dmf_grid_path_device": (C.c_int, [_vp, _p, _p, _p, _i64, _p]),
     "dmf_grid_travel_stats": (C.c_int, [_vp, _p]),
+    "dmf_grid_travel_cost_map": (C.c_int, [_vp, _p, C.c_uint32, _p, _i32, _p]),
+    "dmf_grid_travel_cost_map_device": (C.c_int, [_vp, _p, C.c_uint32, _p, _i32, _p]),
+    "dmf_tour_nearest_neighbour": (C.c_int, [_vp, _p, _i32, _p, _p]),
+    "dmf_tour_nearest_neighbour_device": (C.c_int, [_vp, _p, _i32, _p, _p]),
+    "dmf_tour_two_opt": (C.c_int, [_vp, _p, _i32, _p, _i64, _p]),
+    "dmf_tour_two_opt_device": (C.c_int, [_vp, _p, _i32, _p, _i64, _p]),
+    "dmf_tour": (C.c_int, [_vp, _p, _i32, _p, _i64, _p]),
+    "dmf_tour_device": (C.c_int, [_vp, _p, _i32, _p, _i64, _p]),
+    "dmf_tour_stats": (C.c_int, [_vp, _p]),
     "dmf_cloud_nearest": (C.c_int, [_vp, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _p]),
     "dmf_cloud_nearest_device": (C.c_int, [_vp, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _p]),
     "dmf_cloud_nearest_stats": (C.c_int, [_vp, _p]),

@@ -546,6 +546,69 @@ int dmf_grid_path(dmf_volume* v, const uint32_t* hops, const int32_t* target3, i
 int dmf_grid_path_device(dmf_volume* v, const uint32_t* d_hops, const int32_t* d_target3, int32_t* d_cells,
                          int64_t cap, uint64_t* d_n);
 
+/* The travel cost map of V cells: map[i][j] (int32, V x V, row-major) = the hop
+ * count from cells[i] to cells[j] of the travel field above seeded at cells[i] alone, INT_MAX where
+ * that is DMF_NO_PATH or cells[j] lies outside the grid (a row whose own cell is outside or blocked
+ * is INT_MAX throughout) -- the fused grid's counterpart of dmf_collision_cost_map, with detours,
+ * and what dmf_tour* takes.  cells is V x 3 int32.  One travel field per row into one reused hop
+ * buffer of the volume's scratch, then a gather of the row's V entries; in the device form nothing
+ * crosses to the host but the rounds' own "anything left?" words, and like dmf_grid_travel_device
+ * it WAITS FOR ITS OWN WORK.  V = 0 is DMF_OK and writes nothing.  Null v / dist2, V < 0 and null
+ * cells / map with V > 0 are DMF_ERR_INVALID; V > 46340 is DMF_ERR_RANGE; the volume is checked as
+ * for dmf_grid_travel. */
+int dmf_grid_travel_cost_map(dmf_volume* v, const uint32_t* dist2, uint32_t radius2, const int32_t* cells, int32_t V,
+                             int32_t* map);
+int dmf_grid_travel_cost_map_device(dmf_volume* v, const uint32_t* d_dist2, uint32_t radius2, const int32_t* d_cells,
+                                    int32_t V, int32_t* d_map);
+
+/* An open tour over a cost map: the order in which to visit V views, as the
+ * reference's planners compute it from their cost map -- TSP::NearestNeighborSearch, then
+ * TSP::TwoOptSearch (include/TSPSolver.hpp:76-98, :136-156).  map is V x V int32, row-major,
+ * map[a][b] = the cost of going from a to b: what dmf_collision_cost_map* and
+ * dmf_grid_travel_cost_map* write.  It may be asymmetric and may hold any int32; INT_MAX is "no
+ * edge".  A tour is an OPEN path: V distinct indices, no edge back to the start.
+ *   Nearest neighbour: path[0] = 0; from the current node the next one is the unvisited node with
+ *   the smallest entry below INT_MAX in the current node's row, the lowest index among equals.
+ *   Where every unvisited entry of the row is INT_MAX the reference aborts; here the lowest
+ *   unvisited index is taken (a "forced pick") and counted.
+ *   2-opt: the length of a path is INT_MAX if one of its edges is INT_MAX, else the sum of its
+ *   edges.  The candidates (i, k), 1 <= i < k <= V - 1, are scanned in lexicographic order; the
+ *   first one for which the path with positions i..k reversed is STRICTLY shorter is applied and
+ *   the scan starts again; the solve ends with the scan that finds none.  Position 0 never moves.
+ *   A path of length INT_MAX is not improved by another such path, however many INT_MAX edges go
+ *   away.  max_rounds > 0 ends the solve after that many applied reversals; 0 runs to the end,
+ *   which comes because every reversal lowers an integer length.
+ * Sums are int64 here, so the result is defined for every input; it EQUALS THE REFERENCE'S WHEREVER
+ * THE REFERENCE'S int SUMS DO NOT OVERFLOW, that is where no path's edges below INT_MAX sum to
+ * INT_MAX or more in magnitude.
+ * dmf_tour_nearest_neighbour* writes path; dmf_tour_two_opt* improves the caller's path in place
+ * (any permutation of 0..V-1; the reference starts from 0, 1, 2, ...); dmf_tour* does the first,
+ * then the second.  info5 (uint64, may be NULL) is written, not accumulated: {forced picks (0 for
+ * dmf_tour_two_opt*), reversals applied, 1 if a scan found no improving candidate (never after
+ * nearest neighbour alone, nor when max_rounds ended the solve) else 0, the sum of the final
+ * path's edges below INT_MAX as an int64, the number of its INT_MAX edges}.
+ * The calls need only a CREATED volume, for its device, stream and scratch (28 B per node), like
+ * dmf_cloud_nearest*.  Host forms: host pointers, synchronise.  Device forms: device pointers on
+ * the volume's stream.  2-opt runs in rounds of two launches, and the host has to learn when a
+ * scan found nothing, so the device forms WAIT FOR THEIR OWN WORK like dmf_grid_travel_device;
+ * d_info5 is complete when they return.
+ * V = 0, 1 and 2 are DMF_OK with the only possible path.  A null v, V < 0, max_rounds < 0 and a
+ * null map or path with V > 0 are DMF_ERR_INVALID; V > 46340 (V * V must stay below 2^31) is
+ * DMF_ERR_RANGE and is checked before the pointers.  A path given to dmf_tour_two_opt* that
+ * repeats an index or holds one outside 0..V-1 is DMF_ERR_INVALID: it is checked on the device,
+ * before anything walks it, and left as it was.  Every applied reversal is checked on the device
+ * to have made the path strictly shorter, which is what ends the solve; a round that did not (the
+ * map was changed under the call) ends it with DMF_ERR_DEVICE_CHECK. */
+int dmf_tour_nearest_neighbour(dmf_volume* v, const int32_t* map, int32_t V, int32_t* path, uint64_t* info5);
+int dmf_tour_nearest_neighbour_device(dmf_volume* v, const int32_t* d_map, int32_t V, int32_t* d_path,
+                                      uint64_t* d_info5);
+int dmf_tour_two_opt(dmf_volume* v, const int32_t* map, int32_t V, int32_t* path, int64_t max_rounds, uint64_t* info5);
+int dmf_tour_two_opt_device(dmf_volume* v, const int32_t* d_map, int32_t V, int32_t* d_path, int64_t max_rounds,
+                            uint64_t* d_info5);
+int dmf_tour(dmf_volume* v, const int32_t* map, int32_t V, int32_t* path, int64_t max_rounds, uint64_t* info5);
+int dmf_tour_device(dmf_volume* v, const int32_t* d_map, int32_t V, int32_t* d_path, int64_t max_rounds,
+                    uint64_t* d_info5);
+
 /* Exact nearest neighbour of every point of one cloud in another, and the cloud error built on it
  * (DESIGN.md §4.7): what the reference's tests/ErrorCalc.cpp:71-97 asks of PCL's k-d tree
  * (nearestKSearch(pt, 1, ...)) one point at a time -- how far a reconstruction lies from a model.

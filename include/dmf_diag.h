@@ -79,6 +79,12 @@ int dmf_volume_get_knob(const dmf_volume* v, int32_t knob, int64_t* value);
  * otherwise. */
 int dmf_grid_travel_stats(const dmf_volume* v, uint64_t* stats4);
 
+/* The volume's latest dmf_tour* call: stats4 = {2-opt rounds launched (a round = one scan and one
+ * apply; launched in batches, so the last ones return at once), batches (reads of the "done" word),
+ * reversals applied, the candidates that stood ahead of the applied ones in their scans, summed}.
+ * All 0 after a call that ran no 2-opt. */
+int dmf_tour_stats(const dmf_volume* v, uint64_t* stats4);
+
 /* The volume's latest dmf_cloud_nearest* call (waits for it): stats4 = {reference points examined,
  * shells of cells scanned, the cells of the index, the valid reference points}; the first two are
  * summed over the queries, counted only by a library built with -DDMF_EXP_STATS and 0 otherwise.
