@@ -174,4 +174,90 @@ inline std::vector<unsigned long long int> setCoverBatched(RayTracingEngine engi
   volume.touch();
   return std::vector<unsigned long long int>(sel.begin(), sel.begin() + n);
 }
+
+// ---- candidate views on the device (include/dmf.h: dmf_cloud_downsample, dmf_position_cameras,
+// dmf_grid_surface_views).  The host code above and in <pcl/filters/voxel_grid.h> stays the truth:
+// these give the same bits for xyz, the normals and the poses.  Colour and curvature are not
+// carried: the filtered points hold 0 there.
+using LocationCloud = pcl::PointCloud<pcl::PointXYZRGBNormal>;
+
+inline std::vector<Eigen::Affine3f> poses_from12(const std::vector<float>& poses, size_t m) {
+  std::vector<Eigen::Affine3f> cameras(m, Eigen::Affine3f::Identity());
+  for (size_t i = 0; i < m; ++i)
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 4; ++c) cameras[i](r, c) = poses[12 * i + 4 * r + c];
+  return cameras;
+}
+inline void locations_from(const std::vector<float>& xyz, const std::vector<float>& nrm, size_t m, LocationCloud& out) {
+  out.points.assign(m, pcl::PointXYZRGBNormal());
+  for (size_t i = 0; i < m; ++i) {
+    pcl::PointXYZRGBNormal& p = out.points[i];
+    p.x = xyz[3 * i]; p.y = xyz[3 * i + 1]; p.z = xyz[3 * i + 2];
+    for (int a = 0; a < 3; ++a) p.normal[a] = nrm[3 * i + a];
+  }
+  out.width = (uint32_t)m;
+  out.height = 1;
+}
+
+// PointCloudProcessing::downsample<pcl::PointXYZRGBNormal>(cloud, cloud_filtered, leaf) on the
+// device of `volume` (which need not be constructed)
+inline void downsampleOnDevice(VoxelVolume& volume, LocationCloud::Ptr cloud, LocationCloud::Ptr cloud_filtered,
+                               double leaf) {
+  const size_t n = cloud->points.size();
+  std::vector<float> xyz(3 * n), nrm(3 * n);
+  for (size_t i = 0; i < n; ++i) {
+    const pcl::PointXYZRGBNormal& p = cloud->points[i];
+    xyz[3 * i] = p.x; xyz[3 * i + 1] = p.y; xyz[3 * i + 2] = p.z;
+    for (int a = 0; a < 3; ++a) nrm[3 * i + a] = p.normal[a];
+  }
+  const float l[3] = {(float)leaf, (float)leaf, (float)leaf};
+  uint64_t cnt[3] = {0, 0, 0};
+  dmf_check(dmf_cloud_downsample(volume.handle(), xyz.data(), nrm.data(), (int64_t)n, l, 0, nullptr, nullptr, nullptr, 0,
+                                 cnt));
+  const size_t m = (size_t)cnt[0];
+  std::vector<float> oxyz(3 * m), onrm(3 * m);
+  if (m)
+    dmf_check(dmf_cloud_downsample(volume.handle(), xyz.data(), nrm.data(), (int64_t)n, l, 0, oxyz.data(), onrm.data(),
+                                   nullptr, (int64_t)m, cnt));
+  locations_from(oxyz, onrm, m, *cloud_filtered);
+}
+
+// Algorithms::positionCameras(locations, distance) on the device of `volume`; the flipped normals
+// come back in `locations`, as the host code leaves them.  flip = false: the plain
+// positionCamera(locations, i, distance) loop.
+inline std::vector<Eigen::Affine3f> positionCamerasOnDevice(VoxelVolume& volume, LocationCloud::Ptr locations,
+                                                            unsigned int distance = 300, bool flip = true) {
+  const size_t m = locations->points.size();
+  std::vector<float> xyz(3 * m), nrm(3 * m), poses(12 * m);
+  for (size_t i = 0; i < m; ++i) {
+    const pcl::PointXYZRGBNormal& p = locations->points[i];
+    xyz[3 * i] = p.x; xyz[3 * i + 1] = p.y; xyz[3 * i + 2] = p.z;
+    for (int a = 0; a < 3; ++a) nrm[3 * i + a] = p.normal[a];
+  }
+  dmf_check(dmf_position_cameras(volume.handle(), xyz.data(), nrm.data(), (int64_t)m, distance,
+                                 flip ? 0u : DMF_PLACE_KEEP_NORMALS, poses.data()));
+  for (size_t i = 0; i < m; ++i)
+    for (int a = 0; a < 3; ++a) locations->points[i].normal[a] = nrm[3 * i + a];
+  return poses_from12(poses, m);
+}
+
+// The fused grid's surface -> downsample(leaf) -> positionCameras(distance) in one call, the
+// surface never leaving the device: the candidate locations into `locations`, the poses returned.
+// `logodds` is the int16 grid of the constructed `volume` (x-major, as dmf_fuse_finalize writes it).
+inline std::vector<Eigen::Affine3f> surfaceViews(VoxelVolume& volume, const std::vector<int16_t>& logodds,
+                                                 LocationCloud::Ptr locations, double leaf, unsigned int distance = 300,
+                                                 int occ_threshold = 1, int free_threshold = -1, bool flip = true) {
+  const float l[3] = {(float)leaf, (float)leaf, (float)leaf};
+  const uint32_t pf = flip ? 0u : DMF_PLACE_KEEP_NORMALS;
+  uint64_t cnt[3] = {0, 0, 0};
+  dmf_check(dmf_grid_surface_views(volume.handle(), logodds.data(), occ_threshold, free_threshold, l, 0, distance, pf,
+                                   nullptr, nullptr, nullptr, 0, cnt));
+  const size_t m = (size_t)cnt[0];
+  std::vector<float> poses(12 * m), xyz(3 * m), nrm(3 * m);
+  if (m)
+    dmf_check(dmf_grid_surface_views(volume.handle(), logodds.data(), occ_threshold, free_threshold, l, 0, distance, pf,
+                                     poses.data(), xyz.data(), nrm.data(), (int64_t)m, cnt));
+  locations_from(xyz, nrm, m, *locations);
+  return poses_from12(poses, m);
+}
 }  // namespace dmf_compat

@@ -87,6 +87,12 @@ enum ScratchSlot {
   // the tour (dmf_tour.hip): the control block, the four prefix arrays with the permutation check's
   // bits, and the host forms' map, path and info
   kScToCtl, kScToPre, kScToMap, kScToPath, kScToInfo,
+  // candidate views (dmf_views.hip): the control block, the leaf keys with the point indices, the
+  // segment-head flags with their scan, the leaves' first sorted positions, and the host forms'
+  // staging of the cloud, the leaves, the poses and the counts (the chain's surface cloud lives in
+  // kScSfXyz / kScSfNrm, its locations in kScVwOutXyz / kScVwOutNrm when the caller takes none)
+  kScVwCtl, kScVwKeys, kScVwFlags, kScVwStart, kScVwInXyz, kScVwInNrm, kScVwOutXyz, kScVwOutNrm, kScVwOutPts,
+  kScVwPoses, kScVwCount,
   // brick-owned fusion (dmf_fuse.hip): one block, buffer b of staging slot s at bk_key(b, s)
   kScBkFirst, kScBkEnd = kScBkFirst + 2 * kBkBufCount
 };
@@ -156,6 +162,15 @@ enum { kValueSlotHash = 0, kValueEnumCentroidHash = 1 };
 // the selection order comes back on the host.  Scratch: kScTmp and kScCount.
 int greedy_cover(dmf_volume* v, const uint64_t* d_masks, int P, int64_t words, int min_gain, int32_t* selected,
                  int32_t* nselected);
+// Surface extraction in two steps (dmf_surface.hip), for callers that size a buffer by the count:
+// surface_count leaves the masks, the row counts and their scan in the volume's scratch and writes
+// d_count[2] = {surface cells, solid cells}; surface_emit, after it on the same grid, writes the
+// first min(count, cap) entries of the given outputs; surface_count_host uploads a host grid, counts
+// and reads the counts back (synchronises).
+int surface_count(dmf_volume* v, const int16_t* d_logodds, int32_t occ, int32_t free_thr, uint64_t* d_count);
+int surface_emit(dmf_volume* v, const int16_t* d_logodds, uint64_t* d_hash, float* d_xyz, float* d_nrm, int64_t cap);
+int surface_count_host(dmf_volume* v, const int16_t* logodds, int32_t occ, int32_t free_thr, void** d_grid,
+                       uint64_t cnt[2]);
 // The log-odds ray-cast's argument checks (dmf_raycast.hip): the plain arguments without access to
 // the volume, then check_fuse_call.
 int check_raycast(const dmf_volume* v, const dmf_camera* cam, const void* logodds, const void* poses, int32_t P,

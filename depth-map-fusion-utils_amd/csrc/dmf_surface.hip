@@ -214,7 +214,7 @@ static const char kSfGridLimit[] = "surface extraction is limited to 2048 cells 
 
 // Masks, row counts and their scan (left in the volume's scratch for surface_emit);
 // d_count[2] = {surface cells, solid cells}.
-static int surface_count(dmf_volume* v, const int16_t* d_logodds, int32_t occ, int32_t free_thr, uint64_t* d_count) {
+int surface_count(dmf_volume* v, const int16_t* d_logodds, int32_t occ, int32_t free_thr, uint64_t* d_count) {
   const Geom g = v->geom();
   const GridTiles tl = grid_tiles(g.n);
   const size_t words = 16 * (size_t)tl.ntiles;
@@ -242,7 +242,7 @@ static int surface_count(dmf_volume* v, const int16_t* d_logodds, int32_t occ, i
 }
 
 // After surface_count on the same grid: the first min(count, cap) entries of the given outputs.
-static int surface_emit(dmf_volume* v, const int16_t* d_logodds, uint64_t* d_hash, float* d_xyz, float* d_nrm,
+int surface_emit(dmf_volume* v, const int16_t* d_logodds, uint64_t* d_hash, float* d_xyz, float* d_nrm,
                         int64_t cap) {
   if (cap <= 0 || (!d_hash && !d_xyz && !d_nrm)) return DMF_OK;
   const Geom g = v->geom();
@@ -257,7 +257,7 @@ static int surface_emit(dmf_volume* v, const int16_t* d_logodds, uint64_t* d_has
 }
 
 // Upload the host grid, count, and read the counts back (synchronises).
-static int surface_count_host(dmf_volume* v, const int16_t* logodds, int32_t occ, int32_t free_thr, void** d_grid,
+int surface_count_host(dmf_volume* v, const int16_t* logodds, int32_t occ, int32_t free_thr, void** d_grid,
                               uint64_t cnt[2]) {
   void* dc;
   DMF_TRY(upload_grid(v, logodds, d_grid));

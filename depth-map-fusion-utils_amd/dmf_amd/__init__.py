@@ -512,6 +512,69 @@ class VoxelVolume:
         return SurfaceError(n, nv, float(sums[0]), float(sums[1]) / nv if nv else float("nan"),
                             tuple(int(c) for c in cnt[2:]), d2)
 
+    # -- candidate views: voxel-grid downsample, camera placement and the chain over a fused grid
+    #    (DESIGN.md §4.9), on the GPU
+    @staticmethod
+    def _leaf(leaf):
+        l = np.asarray(leaf)
+        if l.dtype.kind not in "fiu" or l.shape not in ((), (3,)):
+            raise ValueError(f"leaf must be one number or three, got {l.dtype} {l.shape}")
+        l = np.ascontiguousarray(np.broadcast_to(l.astype(np.float32), (3,)))
+        if not (np.isfinite(l).all() and (l > 0).all()):
+            raise ValueError(f"leaf must be finite and > 0 in float32, got {l.tolist()}")
+        return l
+
+    def cloud_downsample(self, xyz, leaf, normals=None, unit_normals=False):
+        """PCL's VoxelGrid over the cloud `xyz` (float32 (n, 3)) with `normals` (float32 (n, 3) or
+        None), as PointCloudProcessing::downsample runs it -> (xyz float32 (m, 3), normals float32
+        (m, 3) or None, points int32 (m,)): one entry per non-empty leaf of size `leaf` (one number or
+        three), in ascending leaf index, holding the float32 mean of the leaf's points (summed in
+        input order) and their number; bit for bit the drop-in's host VoxelGrid.  Points with a
+        non-finite coordinate are skipped.  unit_normals=True renormalises the mean normals (PCL >=
+        1.8).  A grid of more than 2^31 - 1 leaves raises DmfError (DMF_ERR_RANGE).  The volume only
+        lends its device, stream and scratch: it need not be constructed."""
+        p = self._cloud(xyz, "xyz")
+        l = self._leaf(leaf)
+        nn = None
+        if normals is not None:
+            nn = self._cloud(normals, "normals")
+            if nn.shape != p.shape:
+                raise ValueError(f"normals must have xyz's shape {p.shape}, got {nn.shape}")
+        n = p.shape[0]
+        flags = 1 if unit_normals else 0
+        cnt = np.zeros(3, np.uint64)
+        args = (self._h, ptr(p) if n else None, ptr(nn) if n and nn is not None else None, n, ptr(l), flags)
+        check(self._L.dmf_cloud_downsample(*args, None, None, None, 0, ptr(cnt)))
+        m = int(cnt[0])
+        ox, on, op = np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32), np.zeros(m, np.int32)
+        if m:
+            check(self._L.dmf_cloud_downsample(*args, ptr(ox), ptr(on) if nn is not None else None, ptr(op), m,
+                                               ptr(cnt)))
+        return ox, (on if nn is not None else None), op
+
+    def surface_views(self, logodds, leaf, distance_mm=300, occ_threshold=1, free_threshold=-1, unit_normals=False,
+                      flip=True):
+        """Candidate camera poses for the fused grid `logodds` without the surface leaving the
+        device: extract_surface -> cloud_downsample(leaf) -> position_cameras(distance_mm, flip) ->
+        (poses float32 (m, 3, 4), xyz float32 (m, 3), normals float32 (m, 3)): the poses, the
+        candidate locations and their normals as the placement left them.  The poses can go
+        straight into RayTracingEngine.view_gain / next_best_views on the same grid.  flip=False
+        keeps normals that face down (a fused grid has such surfaces; the reference's table-top
+        scans do not)."""
+        lo = self._logodds(logodds)
+        l = self._leaf(leaf)
+        if not 0 <= int(distance_mm) <= 0xFFFFFFFF:
+            raise ValueError(f"distance_mm must fit uint32, got {distance_mm}")
+        cnt = np.zeros(3, np.uint64)
+        args = (self._h, ptr(lo), int(occ_threshold), int(free_threshold), ptr(l), 1 if unit_normals else 0,
+                int(distance_mm), 0 if flip else 1)
+        check(self._L.dmf_grid_surface_views(*args, None, None, None, 0, ptr(cnt)))
+        m = int(cnt[0])
+        poses, xyz, nrm = np.zeros((m, 3, 4), np.float32), np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32)
+        if m:
+            check(self._L.dmf_grid_surface_views(*args, ptr(poses), ptr(xyz), ptr(nrm), m, ptr(cnt)))
+        return poses, xyz, nrm
+
     @property
     def occupied_cells_(self):
         n = C.c_int64(0)
@@ -857,6 +920,27 @@ def collision_cost_map(volume, poses):
     out = np.zeros((V, V), np.int32)
     check(volume._L.dmf_collision_cost_map(volume._h, ptr(poses), V, ptr(out)))
     return out
+
+
+def position_cameras(volume, xyz, normals, distance_mm=300, flip=True):
+    """Algorithms::positionCameras over the locations `xyz` (float32 (m, 3)) with `normals` (float32
+    (m, 3)) -> (poses float32 (m, 3, 4), normals float32 (m, 3)); on the GPU.  With
+    flip=True a normal with z <= 0 is negated first (the returned normals; the argument is not
+    changed), as the reference does in its cloud; then each camera stands distance_mm out along the
+    normal and looks back along it: columns x = (0, -1, 0), y = (1, 0, 0), z = -normal.  flip=False
+    is the plain positionCamera loop.  `volume` supplies the device and stream."""
+    p = VoxelVolume._cloud(xyz, "xyz")
+    nn = np.array(VoxelVolume._cloud(normals, "normals"), np.float32)
+    if nn.shape != p.shape:
+        raise ValueError(f"normals must have xyz's shape {p.shape}, got {nn.shape}")
+    if not 0 <= int(distance_mm) <= 0xFFFFFFFF:
+        raise ValueError(f"distance_mm must fit uint32, got {distance_mm}")
+    m = p.shape[0]
+    poses = np.zeros((m, 3, 4), np.float32)
+    if m:
+        check(volume._L.dmf_position_cameras(volume._h, ptr(p), ptr(nn), m, int(distance_mm), 0 if flip else 1,
+                                             ptr(poses)))
+    return poses, nn
 
 
 def _tour_map(cost_map):

@@ -161,6 +161,14 @@ SIGNATURES = {
     "dmf_cloud_nearest": (C.c_int, [_vp, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _p]),
     "dmf_cloud_nearest_device": (C.c_int, [_vp, _p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _p]),
     "dmf_cloud_nearest_stats": (C.c_int, [_vp, _p]),
+    "dmf_cloud_downsample": (C.c_int, [_vp, _p, _p, _i64, _p, C.c_uint32, _p, _p, _p, _i64, _p]),
+    "dmf_cloud_downsample_device": (C.c_int, [_vp, _p, _p, _i64, _p, C.c_uint32, _p, _p, _p, _i64, _p]),
+    "dmf_position_cameras": (C.c_int, [_vp, _p, _p, _i64, C.c_uint32, C.c_uint32, _p]),
+    "dmf_position_cameras_device": (C.c_int, [_vp, _p, _p, _i64, C.c_uint32, C.c_uint32, _p]),
+    "dmf_grid_surface_views": (C.c_int, [_vp, _p, _i32, _i32, _p, C.c_uint32, C.c_uint32, C.c_uint32, _p, _p, _p, _i64,
+                                         _p]),
+    "dmf_grid_surface_views_device": (C.c_int, [_vp, _p, _i32, _i32, _p, C.c_uint32, C.c_uint32, C.c_uint32, _p, _p,
+                                                _p, _i64, _p]),
     "dmf_cloud_nearest_set_variant": (C.c_int, [_vp, _i32, _i32]),
     "dmf_fuse_counter_cells": (C.c_int, [_vp, _p]),
     "dmf_fuse_counters_to_linear_device": (C.c_int, [_vp, _p, _p]),

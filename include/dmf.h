@@ -651,6 +651,84 @@ int dmf_cloud_nearest_device(dmf_volume* v, const float* d_query, int64_t n, con
                              float* d_dist2, int32_t* d_index, const double* thresholds, int32_t T,
                              uint64_t* d_counts, double* d_sums);
 
+/* Candidate views from an oriented cloud: the voxel-grid downsample that every
+ * planner of the reference runs over its cloud (PointCloudProcessing::downsample, PCL's
+ * VoxelGrid<PointXYZRGBNormal>) and the camera placement that follows it
+ * (Algorithms::positionCameras, Algorithms.hpp:189-234, 281-298), bit for bit what the drop-in's
+ * host code (compat/shims/pcl/filters/voxel_grid.h, compat/Algorithms.hpp) computes, and the
+ * chain surface -> downsample -> placement over a fused grid.
+ *
+ * dmf_cloud_downsample*: xyz[n][3] and normals[n][3] (or NULL) are packed float32, n <= 2^31 - 1;
+ * leaf[3] (a HOST pointer in both forms) is the leaf size, each finite and > 0.  All in float32
+ * with no contraction: inv_a = 1.0f / leaf_a.  A point takes part iff its three coordinates are
+ * finite; other points are skipped everywhere (the bounds too) and their normals are never read.
+ * min_b_a = (int)floorf(min_a * inv_a) and max_b_a likewise over the participating points,
+ * div_a = max_b_a - min_b_a + 1; a point's leaf is i0 + i1 div0 + i2 div0 div1 with
+ * i_a = (int)floorf(p_a * inv_a) - min_b_a.  One entry per non-empty leaf, in ascending leaf,
+ * each output may be NULL:
+ *   out_xyz      3 floats: acc / (float)count, where acc starts at 0.0f and adds the leaf's points
+ *                in ascending input index, one float32 add at a time;
+ *   out_normals  3 floats: the same mean of the normals (a non-finite normal propagates); with
+ *                DMF_DOWNSAMPLE_UNIT_NORMALS in flags (PCL >= 1.8 renormalises) the mean is divided
+ *                by sqrtf(x*x + (y*y + z*z)) unless all three components are zero;
+ *   out_points   int32: the leaf's population.
+ * count[3] = {leaves, participating points, largest leaf population}, whatever the capacity.
+ * A grid of more than 2^31 - 1 leaves (PCL: "leaf size is too small"), or a bound whose leaf
+ * coordinate floorf(. * inv_a) is at or beyond 2^31 in magnitude, is refused: the host form returns
+ * DMF_ERR_RANGE, the device form, which only enqueues, writes count[0] = DMF_LEAVES_REFUSED; no
+ * output is touched in either.
+ * Device form: device pointers, only enqueues on the volume's stream, allocates only when its
+ * scratch (20 B per point, and the sort's) must grow; writes the first min(leaves, cap) entries and
+ * nothing at or past cap, and always d_count[3].  Host form: host pointers, synchronises; cap <
+ * leaves is DMF_ERR_CAPACITY with count[0] = the need and the outputs untouched, except that cap = 0
+ * with NULL outputs is the size query (DMF_OK); count may be NULL.  n = 0, or no finite point,
+ * gives 0 leaves and DMF_OK.  The volume only lends its device, stream and scratch, as for
+ * dmf_cloud_nearest*: an UNCONSTRUCTED volume is fine.  A null v / leaf, a null xyz with n > 0, a
+ * negative n or cap, a leaf that is not finite and > 0, unknown flags, out_normals without normals
+ * and, in the device form, a null d_count are DMF_ERR_INVALID; n >= 2^31 is DMF_ERR_RANGE.
+ *
+ * dmf_position_cameras*: for each of m locations xyz[i] with normal n = normals[i], one pose of 12
+ * floats (rows 0..2 of the camera-to-world transform, as every other call takes them):
+ *   first, unless DMF_PLACE_KEEP_NORMALS is in flags (positionCameras): a normal with n[2] <= 0 is
+ *   negated IN `normals`, all three components (-0.0 flips, NaN does not);
+ *   then (positionCamera(locations, i, distance)): columns x = (0, -1, 0), y = (1, 0, 0), z = -n,
+ *   position_a = (float)((double)((float)(distance_mm / 1000.0) * n_a) + (double)p_a).
+ * DMF_PLACE_KEEP_NORMALS is the plain positionCamera loop of CameraPathGen.cpp:77-81: a fused grid
+ * has surfaces that face down, and flipping those would put the camera behind the surface.  The
+ * volume as above.  Null v, negative m, null pointers with m > 0 and unknown flags are
+ * DMF_ERR_INVALID; m = 0 is DMF_OK.
+ *
+ * dmf_grid_surface_views*: dmf_grid_surface_device (xyz and normals) -> downsample -> placement
+ * over `logodds`, with nothing but counts crossing to the host: poses[cap][12], and the candidate
+ * locations xyz[cap][3] and their normals[cap][3] after the placement's flip (each may be NULL);
+ * count[3] = {views, surface cells, solid cells}.  The poses can go straight into
+ * dmf_view_gain_device, dmf_next_best_views_device or dmf_reverse_visibility_device.  Capacity,
+ * the size query and the refusal as for the downsample (count[0] = DMF_LEAVES_REFUSED).  The device
+ * form reads the surface count back (16 bytes, synchronises once) to size the cloud's scratch
+ * before it enqueues the rest.  The surface call's conditions hold: an unconstructed volume is
+ * DMF_ERR_STATE, more than 2048 cells on an axis DMF_ERR_RANGE. */
+#define DMF_LEAVES_REFUSED 0xFFFFFFFFFFFFFFFFull /* UINT64_MAX */
+#define DMF_DOWNSAMPLE_UNIT_NORMALS 1u
+#define DMF_PLACE_KEEP_NORMALS 1u
+int dmf_cloud_downsample(dmf_volume* v, const float* xyz, const float* normals, int64_t n, const float* leaf,
+                         uint32_t flags, float* out_xyz, float* out_normals, int32_t* out_points, int64_t cap,
+                         uint64_t* count);
+int dmf_cloud_downsample_device(dmf_volume* v, const float* d_xyz, const float* d_normals, int64_t n,
+                                const float* leaf, uint32_t flags, float* d_out_xyz, float* d_out_normals,
+                                int32_t* d_out_points, int64_t cap, uint64_t* d_count);
+int dmf_position_cameras(dmf_volume* v, const float* xyz, float* normals, int64_t m, uint32_t distance_mm,
+                         uint32_t flags, float* poses);
+int dmf_position_cameras_device(dmf_volume* v, const float* d_xyz, float* d_normals, int64_t m, uint32_t distance_mm,
+                                uint32_t flags, float* d_poses);
+int dmf_grid_surface_views(dmf_volume* v, const int16_t* logodds, int32_t occ_threshold, int32_t free_threshold,
+                           const float* leaf, uint32_t downsample_flags, uint32_t distance_mm,
+                           uint32_t placement_flags, float* poses, float* xyz, float* normals, int64_t cap,
+                           uint64_t* count);
+int dmf_grid_surface_views_device(dmf_volume* v, const int16_t* d_logodds, int32_t occ_threshold,
+                                  int32_t free_threshold, const float* leaf, uint32_t downsample_flags,
+                                  uint32_t distance_mm, uint32_t placement_flags, float* d_poses, float* d_xyz,
+                                  float* d_normals, int64_t cap, uint64_t* d_count);
+
 /* ---- multi-GPU merge over RCCL ------------------------
  * Poses shard across ranks, each rank fuses into its own replica of the counters, and
  * the replicas merge with integer collectives (bit-identical to one rank fusing all
